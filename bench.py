@@ -5,6 +5,15 @@ bench.py -- objective evaluations per second of the MI355X swarm generation.
     python bench.py --gpus N --steps K --warmup W          (N > 1: launches its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                             (everything beyond the headline, see below)
+    python bench.py ... --dump-outputs DIR                 (what the last timed step computed, as .npy files)
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up generations,
+the pre-heat, EXACTLY K timed generations, the outputs (--dump-outputs) and the JSON line.  Everything
+else -- the CPU baselines, the live rocprofv3 PMC passes, the kernel variants / far-field /
+imaginary-channel / dense-spectrum / host-pointer extras, the other BASELINE configs, the reference's
+default fit (lone, batched, fit_many, the README pipeline) and, N > 1, the replicas -- runs with
+--full only, after the timed region as before (the CPU legs and the PMC passes before it).
 
 Either form runs one process per GPU.  With WORLD_SIZE unset and --gpus N > 1 this script is the
 launcher: before touching any GPU it starts N rank processes of itself (RANK / LOCAL_RANK /
@@ -30,11 +39,19 @@ update -> batched objective (the hot path, one launch) -> personal-best update -
 resident in HBM before the timed region; stopping tests are disabled so every timed generation
 does full work.
 
-Order of a run: CPU baseline legs first (rank 0, N=1 only; nothing has touched the GPU yet, so
-the Pool.map workers are not children of a GPU process) -> swarm init + W warm-up generations
+Order of a run: [--full: CPU baseline legs first (rank 0, N=1 only; nothing has touched the GPU yet,
+so the Pool.map workers are not children of a GPU process)] -> swarm init + W warm-up generations
 -> >= 0.5 s of objective launches to bring the clocks to their loaded state -> barrier ->
 EXACTLY K timed generations, each objective kernel bracketed by HIP events on its own stream
-and each step by a mark (nmrfit_prof_*) -> barrier -> max over ranks.
+and each step by a mark (nmrfit_prof_*) -> barrier -> max over ranks -> [--dump-outputs: the
+swarm's state and best after the last timed generation] -> [--full: the extras].
+
+--dump-outputs DIR: float64 .npy files of what a caller of the timed path receives after its last
+step (DeviceSwarm.state() and .best()): positions, velocities, personal_best_positions, objective,
+personal_best_objective, particle_index, global_best_position, global_best_objective.  The inputs
+(spectrum, swarm seed) are fixed, so the same arguments give the same outputs on every run.  At most
+64 MB in all: a larger swarm is written as a fixed, seeded sample of its particles.  N > 1: every
+rank writes its own shard's arrays with the suffix _rank<r>, rank 0 the global best.
 
 metric  = particle*gridpoint*peak evaluations per second, whole job.
 roofline: from the objective kernel's own durations INSIDE the timed loop (kernel <= step is
@@ -43,7 +60,8 @@ roofline: from the objective kernel's own durations INSIDE the timed loop (kerne
           under the streaming-operand model (an effective, L2-served rate).
           Fields that come from committed rocprofv3 --pmc passes rather than from this run are
           marked "from_committed_profile".
-cpu_baseline: the oracle (numpy restatement of the reference, 1 core = the reference's
+          A plain run takes these from the committed passes; --full measures them live.
+cpu_baseline (--full): the oracle (numpy restatement of the reference, 1 core = the reference's
           default processes=1), the same through multiprocessing.Pool.map (the reference's
           only parallel mode, utils.py:182) and the plain-C OpenMP oracle, on a bounded sample
           of the same workload.
@@ -107,7 +125,19 @@ def parse():
     ap.add_argument("--launch-timeout", type=float, default=300.0, metavar="SECONDS",
                     help="N > 1: deadline of the self-launcher for the whole run, and of every rank for reaching the "
                          "timed region (rendezvous, RCCL communicator, first collective); 0 disables")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baselines, live PMC passes, kernel variants "
+                         "and the other extras, other configs, the reference's default fits, replicas (N > 1).  "
+                         "--cpu-seconds, --cpu-pool, --no-extras, --no-other-configs and --no-pmc act on these; "
+                         "without --full they are all off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (swarm state and best) to "
+                         "DIR/<name>.npy, float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs and the line -- nothing else
+        args.cpu_seconds, args.pmc, args.no_extras, args.other_configs = 0.0, False, True, False
+    return args
 
 
 # ---- launcher (N > 1 without a launcher's environment) -------------------------------------------
@@ -403,6 +433,30 @@ def live_pmc_passes(timeout_s=90.0):
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
     return out
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000      # --dump-outputs: all files of a run together (npy headers included)
+
+
+def dump_outputs(out_dir, state, best, rank=0, world=1, offset=0):
+    """--dump-outputs: the swarm after the last timed generation as a caller of the timed path receives it
+    (DeviceSwarm.state(), DeviceSwarm.best()), one float64 .npy per array.  A shard too large for its share of the
+    budget is written as a fixed, seeded sample of its particles; `particle_index` holds their global indices.
+    Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    S, D = state["x"].shape
+    row_bytes = (3 * D + 3) * 8                          # x, v, p rows + fx, fp, particle_index
+    keep = max(1, min(S, (DUMP_BUDGET_BYTES // world - (D + 1) * 8 - 4096) // row_bytes))
+    idx = np.arange(S) if keep == S else np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+    sfx = "" if world == 1 else "_rank%d" % rank
+    out = [("positions" + sfx, state["x"][idx]), ("velocities" + sfx, state["v"][idx]),
+           ("personal_best_positions" + sfx, state["p"][idx]), ("objective" + sfx, state["fx"][idx]),
+           ("personal_best_objective" + sfx, state["fp"][idx]), ("particle_index" + sfx, idx + offset)]
+    if rank == 0:
+        out += [("global_best_position", best[0]), ("global_best_objective", [best[1]])]
+    for name, a in out:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return [name for name, _ in out]
 
 
 def stats(a):
@@ -721,7 +775,10 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     st = sw.status()
     geom = ev.last_launch()
-    ev.upload(d_x, sw.state()["x"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sw.state(), sw.best(), rank, world, rank * S_local)
+    if args.full:
+        ev.upload(d_x, sw.state()["x"])      # the extras below run on the final swarm positions
 
     # ---- extras on the final swarm positions (rank 0, after the timed region) ---------------
     variants = farfield = host_ms = others = None  # (default_fit below)

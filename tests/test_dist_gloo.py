@@ -63,10 +63,22 @@ def _single(S, maxiter, seed):
 
 @pytest.mark.parametrize("world,S", [(2, 20), (3, 17)])
 def test_sharded_swarm_over_gloo_equals_single_rank(tmp_path, world, S):
-    import torch.multiprocessing as mp
+    # the ranks import torch in their own processes, never this one: torch ships its own HIP runtime and librccl
+    # under the system's sonames, and once loaded here the in-process RCCL tests of a whole-suite run would get them
+    import multiprocessing
+    ctx = multiprocessing.get_context("spawn")
     port = _free_port()
     maxiter, seed = 15, 4242
-    mp.spawn(_worker, args=(world, port, S, maxiter, seed, str(tmp_path)), nprocs=world, join=True)
+    ps = [ctx.Process(target=_worker, args=(r, world, port, S, maxiter, seed, str(tmp_path))) for r in range(world)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join(timeout=300)
+    for p in ps:
+        if p.exitcode is None:
+            p.terminate()
+            p.join(10)
+    assert [p.exitcode for p in ps] == [0] * world
     x1, f1, sw1 = _single(S, maxiter, seed)
     xs = []
     for r in range(world):

@@ -15,6 +15,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +48,8 @@ def _free_port():
 
 
 def test_bench_paths_agree():
-    common = ["--steps", "5", "--warmup", "2", "--cpu-seconds", "0", "--workload", "C2", "--preheat-seconds", "0.1"]
+    common = ["--steps", "5", "--warmup", "2", "--cpu-seconds", "0", "--workload", "C2", "--preheat-seconds", "0.1",
+              "--full"]
     plain = _run([sys.executable, "bench.py", "--swarm-per-gpu", "512"] + common, {})
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "roofline_streaming", "step_ms", "kernel_ms",
@@ -111,6 +113,37 @@ def test_bench_paths_agree():
     _check_replicas(three, 3, 12)
 
 
+def test_plain_run_is_lean_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run (no --full) times exactly --steps generations and its line carries the headline only; with
+    --dump-outputs it writes the swarm after the last timed generation, float64, and the same arguments give the same
+    outputs bit for bit."""
+    args = ["--steps", "6", "--warmup", "2", "--workload", "C2", "--swarm-per-gpu", "512", "--preheat-seconds", "0.1"]
+    lines, dumps = [], []
+    for k in range(2):
+        d = str(tmp_path / str(k))
+        lines.append(_run([sys.executable, "bench.py", "--dump-outputs", d] + args, {}))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "kernel_ms"):
+        assert key in line, key
+    assert line["steps"] == 6 and line["step_ms"]["n"] == 6 and line["kernel_ms"]["n"] == 6
+    assert line["config"]["generations_done"] == 8 and "error" not in line
+    assert line["value"] == pytest.approx(512 * 4096 * 6 / (line["ms_per_step"] * 1e-3))
+    for key in ("cpu_baseline", "variants", "imaginary_channel", "dense_spectrum", "other_configs", "every_unit",
+                "reference_default_fit", "reference_default_fit_batched", "readme_pipeline", "host_pointer_call",
+                "value_incl_pcie", "pmc_live_errors", "replicas"):
+        assert key not in line, key
+    out = dumps[0]
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["positions"].shape == out["velocities"].shape == out["personal_best_positions"].shape == (512, 22)
+    assert out["objective"].shape == out["personal_best_objective"].shape == (512,)
+    assert np.all(out["personal_best_objective"] <= out["objective"])
+    assert out["global_best_objective"][0] == line["config"]["swarm_best_f"] == out["personal_best_objective"].min()
+    assert sorted(out) == sorted(dumps[1])
+    for name in out:
+        np.testing.assert_array_equal(out[name], dumps[1][name], err_msg=name)
+
+
 def _check_replicas(line, world, jobs):
     """the N > 1 line carries BOTH multi-GPU modes -- the swarm-sharded `value` (with `scaling_model`)
     and the spectra-parallel replicas, every rank its own spectra through fit_many / fit_many(shard=True)."""
@@ -155,7 +188,7 @@ def test_bench_says_so_when_rccl_is_unavailable():
 def test_c4_rehearsal_four_ranks_on_one_gpu():
     """C4's per-GPU shape (4096 particles x 65536 points x 24 peaks per rank) with 4 ranks on one
     device through the self-launcher, against the one-rank 16384-particle run: same swarm best."""
-    common = ["--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-extras", "--preheat-seconds", "0.1"]
+    common = ["--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-extras", "--preheat-seconds", "0.1", "--full"]
     four = _run([sys.executable, "bench.py", "--gpus", "4", "--swarm-per-gpu", "4096"] + common,
                 {"NMRFIT_BENCH_BACKEND": "host"})
     one = _run([sys.executable, "bench.py", "--swarm-per-gpu", "16384"] + common, {})
@@ -210,7 +243,7 @@ def test_bench_line_carries_live_pmc_counters():
     same script under `rocprofv3 --kernel-trace --pmc`, started before the parent touches the GPU --
     not echoed from a committed file; so is the far-field kernel's entry in `fit_default`."""
     d = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--cpu-seconds", "0", "--no-other-configs",
-              "--preheat-seconds", "0.2"], {})
+              "--preheat-seconds", "0.2", "--full"], {})
     r, fd = d["roofline"], d["fit_default"]
     v = r
     if "pmc_live_errors" in d:

@@ -381,5 +381,10 @@ def test_bench_rank_with_an_impossible_device_fails_before_the_rendezvous():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-seconds", "0"], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert out.returncode == 6, (out.returncode, out.stderr[-1500:])
-    assert "bench.py rank 1/2: no HIP device is visible to local rank 1 (HIP_VISIBLE_DEVICES=)" in out.stderr
+    # every visibility variable the rank sees is named, HIP_VISIBLE_DEVICES first (a GPU machine may also export ROCR_ /
+    # CUDA_VISIBLE_DEVICES: they are not unset here, they are expected in the message)
+    shown = " ".join("%s=%s" % (k, env[k]) for k in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+                     if k in env)
+    assert shown.startswith("HIP_VISIBLE_DEVICES= ") or shown == "HIP_VISIBLE_DEVICES="
+    assert "bench.py rank 1/2: no HIP device is visible to local rank 1 (%s)" % shown in out.stderr
     assert not out.stdout.strip()
