@@ -42,7 +42,7 @@ static_assert(kWave == 64 && kPointsPerLane % 2 == 0, "grid_slot assumes wave64 
 
 // Per-(particle, peak) constants staged in LDS: see objective.hip.
 struct PeakLor {
-    double ihw;   // 2/width (|t| capped at 1e18)
+    double ihw;   // 2/width (|t| capped at 1e18: below that floor width, al and ag2 are the floor width's too)
     double c;     // -(loc - w0) * ihw        so that t = (w_j - w0)*ihw + c
     double al;    // area*r*(2/(pi*width))    Lorentzian amplitude
     double ag2;   // 2*area*(1-r)*(2/width)*sqrt(ln2/pi)   Gaussian amplitude, factor 2 folds exp2(1)

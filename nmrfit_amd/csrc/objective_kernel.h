@@ -230,15 +230,19 @@ __device__ __forceinline__ void objective_body(
         const double width = x[4 + 3 * kx], loc = x[5 + 3 * kx], a = x[6 + 3 * kx];
         const double ihw = 2.0 / width;
         const double locc = loc - w0;
-        // |t| <= 1e18 keeps the grouped denominators finite; the cap only engages for widths
-        // below 2e-18 of the spectral span, where L and G are 0 to 1e-36 either way
+        // |t| <= 1e18 keeps the grouped denominators finite: a width below 2e-18 of the spectral span
+        // (|2/width| > lim) is evaluated as the floor width 2/lim, the WHOLE record of it (amplitudes too),
+        // so the line is consistent in both channels: its dispersion tail a/(pi (w-loc)) does not depend on
+        // the width and stays exact; the real tail is that of the floor width (DESIGN.md "Needle widths")
         const double lim = 1.0e18 / (wspan + fabs(locc));
+        // (width 0: the amplitudes stay infinite, f non-finite like the reference's)
         const double it = (fabs(ihw) > lim) ? copysign(lim, ihw) : ihw;
+        const double ia = __builtin_isinf(ihw) ? ihw : it;
         PeakLor rec;
         rec.ihw = it;
         rec.c = -locc * it;
-        rec.al = a * r * ihw * kInvPi;                            // a*r*(2/(pi*width))
-        rec.ag2 = 2.0 * a * (1.0 - r) * ihw * kSqrtLn2OverPi;     // 2 * a*(1-r)*(2/width)*sqrt(ln2/pi)
+        rec.al = a * r * ia * kInvPi;                             // a*r*(2/(pi*width))
+        rec.ag2 = 2.0 * a * (1.0 - r) * ia * kSqrtLn2OverPi;      // 2 * a*(1-r)*(2/width)*sqrt(ln2/pi)
         if (have) lor[k] = rec;
         // window bounds in f32, rounded outwards (a slightly wider window is still exact)
         const double gw = kGaussWindow * fabs(width);

@@ -24,11 +24,12 @@ __device__ __forceinline__ PeakLor peak_record(const double *__restrict__ x, int
     const double ihw = 2.0 / width;
     const double locc = loc - w0;
     const double lim = 1.0e18 / (wspan + fabs(locc));
-    PeakLor rec;
+    PeakLor rec;   // (a width below the floor: the record of the floor width, as in objective_kernel.h)
     rec.ihw = (fabs(ihw) > lim) ? copysign(lim, ihw) : ihw;
     rec.c = -locc * rec.ihw;
-    rec.al = a * r * ihw * kInvPi;
-    rec.ag2 = 2.0 * a * (1.0 - r) * ihw * kSqrtLn2OverPi;
+    const double ia = __builtin_isinf(ihw) ? ihw : rec.ihw;   // (width 0: non-finite, like the reference)
+    rec.al = a * r * ia * kInvPi;
+    rec.ag2 = 2.0 * a * (1.0 - r) * ia * kSqrtLn2OverPi;
     return rec;
 }
 
