@@ -279,6 +279,38 @@ int nmrfit_batch_best(nmrfit_batch *batch, double *x_best, double *f_best);
 int nmrfit_batch_contributions(nmrfit_batch *batch, const int64_t *Nout, const double *w_out, double *real_out,
                                double *imag_out, double *fit_out, double *data_out);
 
+/* ---- automatic phase correction (opt-in: Data.shift_phase stays the reference's host path) ----------------------------
+ * Entry points added within ABI 6: additive, nothing existing changes, and the version number 6 is pinned by the plain-C
+ * client's check (tests/test_c_client.py).  A binding detects them by symbol lookup (dlsym; ctypes hasattr).
+ * The first stage of the reference's per-spectrum script (README.md:40: data.shift_phase(method='auto'), ahead of
+ * select_peaks and fit) for a batch of S spectra of any lengths, laid out one after the other as in
+ * nmrfit_batch_create_ragged: N holds S lengths (each >= 2), u and v the spectra's real and imaginary parts (spectrum k's
+ * N[k] points at offset N[0] + ... + N[k-1]).  fp64 throughout; every reduction has a fixed order that depends on N[k]
+ * alone, so a spectrum's values are bit-identical run to run and alone or in any batch.  1 <= S <= 65535 per call (the
+ * spectra index a launch's grid); the Python layer cuts longer lists into several calls.
+ *   NMRFIT_PHASE_ACME          the ACME score of (p0, p1) in degrees (nmrfit/proc_autophase.py:142-187)
+ *   NMRFIT_PHASE_PEAK_MINIMA   the peak-minima score of (p0, p1) in degrees (proc_autophase.py:190-219); where the window
+ *                              left of the tallest point is empty (numpy's np.min raises there) the spectrum's status
+ *                              is 1 and the score NaN
+ *   NMRFIT_PHASE_BRUTE_LEVEL   the per-angle test of Data._brute_phase (nmrfit/containers.py:98-110) for a rotation
+ *                              factor (c, s) = exp(i angle) the caller computes: the level error
+ *                              sqrt((mean V[:n] - mean V[-n:])^2), n = max(1, N // 5000), when
+ *                              max(V) > |min(V)|, else NaN.  Means of at most 128 points (N < 645000; else
+ *                              NMRFIT_E_UNSUPPORTED).  V = real((c + i s)(u + i v)) is rounded as fma(c, u, -(s v)),
+ *                              as numpy's FMA complex multiply rounds it (x86-64 with AVX2 / AVX-512). */
+enum { NMRFIT_PHASE_ACME = 0, NMRFIT_PHASE_PEAK_MINIMA = 1, NMRFIT_PHASE_BRUTE_LEVEL = 2 };
+/* score[k*M + m] = score of candidate cand[2 (k*M + m) .. +1] for spectrum k; status: S values (0 ok, 1 an empty
+ * peak-minima window for some candidate).  Replaces each evaluation scipy's fmin makes in proc_autophase.py:134 and the
+ * loop body of containers.py:104-109. */
+int nmrfit_phase_scores(int device, int kind, int32_t S, const int64_t *N, const double *u, const double *v,
+                        int32_t M, const double *cand, double *score, int32_t *status);
+/* scipy.optimize.fmin(score, x0, disp=False) of approximate_phase / autops (proc_autophase.py:71-139) for every spectrum,
+ * one launch, one workgroup per spectrum: x0 and x are S x 2 in degrees; f, nfev, nit what fmin(full_output=True)
+ * returns; status 0 ok, 1 an empty peak-minima window met (the reference raises there; x, f are the simplex so far).
+ * kind: ACME or PEAK_MINIMA. */
+int nmrfit_phase_estimate(int device, int kind, int32_t S, const int64_t *N, const double *u, const double *v,
+                          const double *x0, double *x, double *f, int32_t *nfev, int32_t *nit, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

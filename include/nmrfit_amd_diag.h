@@ -128,6 +128,14 @@ int nmrfit_batch_geometry(const nmrfit_batch *batch, int32_t *mode, int32_t *wav
 /* swarm state of fit k (any pointer may be NULL): x, v, p are S x (4 + 3 P[k]); fx, fp are S */
 int nmrfit_batch_get_state(nmrfit_batch *batch, int32_t k, double *x, double *v, double *p, double *fx, double *fp);
 
+/* ---- automatic phase correction: the optimiser alone ---------------------------------------------------------------
+ * The device Nelder-Mead of nmrfit_phase_estimate driven by an analytic score instead of a spectrum: Rosenbrock in
+ * (p0, p1), (1 - p0)^2 + 100 (p1 - p0^2)^2 as python evaluates it, computed on the device with contraction off.  It
+ * touches no data, so the optimiser can be compared bit for bit with scipy.optimize.fmin(..., full_output=True).  x0, x:
+ * S x 2; f, nfev, nit: S values. */
+int nmrfit_diag_phase_nm_rosenbrock(int device, int32_t S, const double *x0, double *x, double *f, int32_t *nfev,
+                                    int32_t *nit);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ VARIANT_NOREC = 7
 VARIANT_FARFIELD32 = 8     # opt-in mixed precision: the far-field kernel's shared polynomial in packed fp32
 HANDOVER_FAST, HANDOVER_FENCED, HANDOVER_TWO_LAUNCH = 0, 1, 2
 ABI_VERSION = 6
+PHASE_ACME, PHASE_PEAK_MINIMA, PHASE_BRUTE_LEVEL = 0, 1, 2
 _VARIANT_NAMES = {"default": 0, "baseline": 1, "noskip": 2, "single": 3, "quad": 4, "staged": 5, "farfield": 6,
                   "norec": 7, "farfield32": 8}
 
@@ -130,6 +131,9 @@ ALL_SIGNATURES = {
     "nmrfit_batch_set_geometry": [_VP, _INT],
     "nmrfit_batch_geometry": [_VP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I64)],
     "nmrfit_batch_get_state": [_VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_phase_scores": [_INT, _INT, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP],
+    "nmrfit_phase_estimate": [_INT, _INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_diag_phase_nm_rosenbrock": [_INT, _I32, _VP, _VP, _VP, _VP, _VP],
 }
 
 _DIAG_NAMES = (
@@ -139,7 +143,7 @@ _DIAG_NAMES = (
     "nmrfit_pso_set_fused_pbest", "nmrfit_pso_set_fused_tail", "nmrfit_pso_last_launches", "nmrfit_pso_get_state",
     "nmrfit_comm_describe", "nmrfit_comm_all_gather_dev", "nmrfit_comm_all_reduce_host", "nmrfit_comm_barrier",
     "nmrfit_diag_ab_build", "nmrfit_batch_step", "nmrfit_batch_synchronize", "nmrfit_batch_set_geometry",
-    "nmrfit_batch_geometry", "nmrfit_batch_get_state")
+    "nmrfit_batch_geometry", "nmrfit_batch_get_state", "nmrfit_diag_phase_nm_rosenbrock")
 DIAG_SIGNATURES = {k: ALL_SIGNATURES[k] for k in _DIAG_NAMES}
 SIGNATURES = {k: v for k, v in ALL_SIGNATURES.items() if k not in DIAG_SIGNATURES}
 

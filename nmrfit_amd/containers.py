@@ -103,3 +103,38 @@ class Data:
         main = areas[areas >= mean].sum()
         sats = areas[areas < mean].sum()
         return sats / (main + sats)
+
+
+def shift_phase_many(datas, method='auto', p0=0.0, p1=0.0, step=np.pi / 360, device=0):
+    """``for d in datas: d.shift_phase(method, p0, p1, step)`` with the phase search of all of them on the GPU (opt-in;
+    Data.shift_phase stays the host path).  Sets p0, p1 (radians) and V, I on every object with ``u``, ``v``:
+    'auto' runs the ACME optimisation of every spectrum in one launch (from (0, 0), as shift_phase does), 'brute' the
+    level test of every angle of np.arange(-pi, pi, step) for every spectrum in one launch and keeps the first strict
+    minimum in the reference's loop order, 'manual' takes p0, p1 as given.  V and I come from the host ps2, bit-identical
+    to shift_phase for the same p0, p1.  u and v are phased in float64 (float32 input too).
+
+    'brute' picks the host loop's angle exactly where numpy's complex multiply runs its FMA loop (x86-64 with AVX2 or
+    AVX-512; the device rounds the rotation as that loop does, proc_autophase.brute_levels), and refuses spectra of
+    645000 points or more (NmrfitError: the level means of longer spectra would take numpy's recursive pairwise order).
+    Any number of spectra: the library takes at most 65535 per call and the list is cut into such calls."""
+    datas = list(datas)
+    choice = method.lower()
+    if choice == 'manual':
+        ps = [(p0, p1)] * len(datas)
+    elif choice == 'auto':
+        x = proc_autophase.estimate_many([np.asarray(d.u, dtype=np.float64) + 1j * np.asarray(d.v, dtype=np.float64)
+                                          for d in datas], 'acme', device=device)[0]
+        ps = [(a * np.pi / 180, b * np.pi / 180) for a, b in x]
+    elif choice == 'brute':
+        angles = np.arange(-np.pi, np.pi, step)
+        err = proc_autophase.brute_levels([d.u for d in datas], [d.v for d in datas], angles, device=device)
+        ps = []
+        for row in err:
+            ok = row < np.inf                      # (NaN: not upright; the host loop's `err < best_err` is False there)
+            ps.append((angles[np.flatnonzero(row == row[ok].min())[0]] if ok.any() else 0, 0.0))
+    else:
+        raise ValueError("Method must be 'auto', 'brute', or 'manual'.")
+    for d, (a, b) in zip(datas, ps):
+        d.p0, d.p1 = a, b
+        d.V, d.I = proc_autophase.ps2(d.u, d.v, d.p0, d.p1)
+    return datas
