@@ -297,7 +297,8 @@ int nmrfit_batch_contributions(nmrfit_batch *batch, const int64_t *Nout, const d
  *                              sqrt((mean V[:n] - mean V[-n:])^2), n = max(1, N // 5000), when
  *                              max(V) > |min(V)|, else NaN.  Means of at most 128 points (N < 645000; else
  *                              NMRFIT_E_UNSUPPORTED).  V = real((c + i s)(u + i v)) is rounded as fma(c, u, -(s v)),
- *                              as numpy's FMA complex multiply rounds it (x86-64 with AVX2 / AVX-512). */
+ *                              as numpy's FMA complex multiply rounds it (x86-64 with AVX2 / AVX-512).
+ *                              nmrfit_phase_brute_levels takes n from the caller instead. */
 enum { NMRFIT_PHASE_ACME = 0, NMRFIT_PHASE_PEAK_MINIMA = 1, NMRFIT_PHASE_BRUTE_LEVEL = 2 };
 /* score[k*M + m] = score of candidate cand[2 (k*M + m) .. +1] for spectrum k; status: S values (0 ok, 1 an empty
  * peak-minima window for some candidate).  Replaces each evaluation scipy's fmin makes in proc_autophase.py:134 and the
@@ -310,6 +311,14 @@ int nmrfit_phase_scores(int device, int kind, int32_t S, const int64_t *N, const
  * kind: ACME or PEAK_MINIMA. */
 int nmrfit_phase_estimate(int device, int kind, int32_t S, const int64_t *N, const double *u, const double *v,
                           const double *x0, double *x, double *f, int32_t *nfev, int32_t *nit, int32_t *status);
+/* The brute level (NMRFIT_PHASE_BRUTE_LEVEL) with the mean length n_mean[k] of each spectrum given by the caller:
+ * Data._brute_phase takes n = max(1, int(len(self.V) / 5000)) from the V it holds before its scan, and select_bounds
+ * crops u, v but not V, so n need not follow from N[k].  Python's slices V[:n], V[-n:] stop at N[k]: where
+ * n_mean[k] > N[k] both means are over all N[k] points and the error is 0.  1 <= n_mean[k] <= 128 (a larger mean
+ * length: NMRFIT_E_UNSUPPORTED).  score as in nmrfit_phase_scores; there is no status (the level test has no empty
+ * window). */
+int nmrfit_phase_brute_levels(int device, int32_t S, const int64_t *N, const int64_t *n_mean, const double *u,
+                              const double *v, int32_t M, const double *cand, double *score);
 
 #ifdef __cplusplus
 }

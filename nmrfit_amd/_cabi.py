@@ -133,6 +133,7 @@ ALL_SIGNATURES = {
     "nmrfit_batch_get_state": [_VP, _I32, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_phase_scores": [_INT, _INT, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP],
     "nmrfit_phase_estimate": [_INT, _INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_phase_brute_levels": [_INT, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
     "nmrfit_diag_phase_nm_rosenbrock": [_INT, _I32, _VP, _VP, _VP, _VP, _VP],
 }
 

@@ -114,9 +114,12 @@ def shift_phase_many(datas, method='auto', p0=0.0, p1=0.0, step=np.pi / 360, dev
     to shift_phase for the same p0, p1.  u and v are phased in float64 (float32 input too).
 
     'brute' picks the host loop's angle exactly where numpy's complex multiply runs its FMA loop (x86-64 with AVX2 or
-    AVX-512; the device rounds the rotation as that loop does, proc_autophase.brute_levels), and refuses spectra of
-    645000 points or more (NmrfitError: the level means of longer spectra would take numpy's recursive pairwise order).
-    Any number of spectra: the library takes at most 65535 per call and the list is cut into such calls."""
+    AVX-512; the device rounds the rotation as that loop does, proc_autophase.brute_levels).  Its mean length is the
+    host's, n = max(1, int(len(d.V) / 5000)) from the V the object holds before the scan: select_bounds crops u, v but
+    leaves V, so on a cropped Data n comes from the uncropped length (or from the u of the last shift_phase), not from
+    len(u).  It refuses a mean length above 128, len(V) >= 645000 (NmrfitError: longer means would take numpy's
+    recursive pairwise order).  Any number of spectra: the library takes at most 65535 per call and the list is cut
+    into such calls."""
     datas = list(datas)
     choice = method.lower()
     if choice == 'manual':
@@ -127,7 +130,8 @@ def shift_phase_many(datas, method='auto', p0=0.0, p1=0.0, step=np.pi / 360, dev
         ps = [(a * np.pi / 180, b * np.pi / 180) for a, b in x]
     elif choice == 'brute':
         angles = np.arange(-np.pi, np.pi, step)
-        err = proc_autophase.brute_levels([d.u for d in datas], [d.v for d in datas], angles, device=device)
+        n = [max(1, int(len(d.V) / 5000)) for d in datas]        # (Data._brute_phase: before its scan)
+        err = proc_autophase.brute_levels([d.u for d in datas], [d.v for d in datas], angles, device=device, n=n)
         ps = []
         for row in err:
             ok = row < np.inf                      # (NaN: not upright; the host loop's `err < best_err` is False there)

@@ -232,8 +232,10 @@ __device__ double numpy_block_sum(const Spectrum &sp, int64_t first, int64_t n, 
 }
 
 // the per-angle test of Data._brute_phase (containers.py:98-110) for the rotation factor (c, s) = exp(i angle):
-// V = real(exp(i angle) (u + i v)); err = sqrt((mean(V[:n]) - mean(V[-n:]))^2), n = max(1, N // 5000); err where max(V) > |min(V)|, else NaN
-__device__ double score_brute(const Spectrum &sp, double c, double s, Lds &lds, int nt)
+// V = real(exp(i angle) (u + i v)); err = sqrt((mean(V[:n]) - mean(V[-n:]))^2); err where max(V) > |min(V)|, else NaN.
+// n is the mean length the host takes from len(self.V) before its scan (not from N: select_bounds crops u, v and leaves
+// V alone); python clips both slices at N, so the means are over min(n, N) points.
+__device__ double score_brute(const Spectrum &sp, double c, double s, int64_t n_mean, Lds &lds, int nt)
 {
     const int64_t N = sp.N;
     const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave, nw = nt / kWave;
@@ -260,7 +262,7 @@ __device__ double score_brute(const Spectrum &sp, double c, double s, Lds &lds, 
         mx = max_nan(mx, lds.red[2 * w]);
         mn = min_nan(mn, lds.red[2 * w + 1]);
     }
-    const int64_t n = std::max<int64_t>(1, N / 5000);
+    const int64_t n = std::min<int64_t>(n_mean, N);
     const double nd = (double)n;
     const double d = numpy_block_sum(sp, 0, n, c, s) / nd - numpy_block_sum(sp, N - n, n, c, s) / nd;
     const double err = sqrt(d * d);
@@ -276,24 +278,30 @@ __device__ __forceinline__ Spectrum spectrum_of(const double *u, const double *v
     return sp;
 }
 
+// the brute level's mean length when the caller gives none: the host's n for a V as long as u
+__host__ __device__ inline int64_t brute_default_mean(int64_t N) { return N / 5000 > 1 ? N / 5000 : 1; }
+
 template <int KIND>
-__device__ __forceinline__ double evaluate(const Spectrum &sp, double a, double b, Lds &lds, int nt, bool *empty)
+__device__ __forceinline__ double evaluate(const Spectrum &sp, double a, double b, Lds &lds, int nt, bool *empty,
+                                           int64_t n_mean = 0)
 {
     *empty = false;
     if (KIND == kScoreAcme) return score_acme(sp, a, b, lds, nt);
     if (KIND == kScorePeakMinima) return score_peak_minima(sp, a, b, lds, nt, empty);
-    if (KIND == kScoreBrute) return score_brute(sp, a, b, lds, nt);
+    if (KIND == kScoreBrute) return score_brute(sp, a, b, n_mean, lds, nt);
     // the optimiser's test score: Rosenbrock, as python evaluates (1 - x)**2 + 100*(y - x**2)**2
     const double p = 1.0 - a, q = b - a * a;
     return p * p + 100.0 * (q * q);
 }
 
-// one score per (candidate, spectrum) workgroup: blockIdx.x = candidate, blockIdx.y = spectrum
+// one score per (candidate, spectrum) workgroup: blockIdx.x = candidate, blockIdx.y = spectrum.  n_mean: the brute
+// level's mean length per spectrum (null: brute_default_mean(N)); unused by the other scores.
 template <int KIND>
 __global__ __launch_bounds__(kPhaseMaxThreads) void phase_scores_kernel(const double *__restrict__ u, const double *__restrict__ v,
                                                                         const int64_t *__restrict__ off, int32_t M,
                                                                         const double *__restrict__ cand, double *__restrict__ score,
-                                                                        int32_t *__restrict__ empty_out)
+                                                                        int32_t *__restrict__ empty_out,
+                                                                        const int64_t *__restrict__ n_mean)
 {
     __shared__ Lds lds;
     const int k = blockIdx.y;
@@ -301,7 +309,8 @@ __global__ __launch_bounds__(kPhaseMaxThreads) void phase_scores_kernel(const do
     const Spectrum sp = spectrum_of(u, v, off, k);
     const int nt = phase_threads(sp.N);
     bool empty = false;
-    const double f = evaluate<KIND>(sp, cand[2 * slot], cand[2 * slot + 1], lds, nt, &empty);
+    const int64_t n = KIND == kScoreBrute ? (n_mean ? n_mean[k] : brute_default_mean(sp.N)) : 0;
+    const double f = evaluate<KIND>(sp, cand[2 * slot], cand[2 * slot + 1], lds, nt, &empty, n);
     if (threadIdx.x == 0) {
         score[slot] = f;
         empty_out[slot] = empty ? 1 : 0;
@@ -566,6 +575,43 @@ int run_nm(int device, int kind, int32_t S, const std::vector<int64_t> &off, con
     return NMRFIT_OK;
 }
 
+// one phase_scores_kernel launch over (M candidates) x (S spectra); empty: S x M flags (peak minima's empty window)
+int run_scores(int device, int kind, int32_t S, const std::vector<int64_t> &off, const double *u, const double *v,
+               int32_t M, const double *cand, const int64_t *n_mean, double *score, int32_t *empty)
+{
+    int rc = check_device(device);
+    if (rc != NMRFIT_OK) return rc;
+    StreamLease lease(device);
+    NMRFIT_HIP(take_stream(device, &lease.s));
+    hipStream_t st = lease.s;
+    Scratch mem;
+    double *d_u = nullptr, *d_v = nullptr, *d_c = nullptr, *d_s = nullptr;
+    int64_t *d_off = nullptr, *d_n = nullptr;
+    int32_t *d_e = nullptr;
+    const size_t SM = (size_t)S * (size_t)M;
+    if ((rc = upload_spectra(st, mem, off, u, v, &d_u, &d_v, &d_off)) != NMRFIT_OK) return rc;
+    NMRFIT_HIP(mem.alloc(&d_c, 2 * SM));
+    NMRFIT_HIP(mem.alloc(&d_s, SM));
+    NMRFIT_HIP(mem.alloc(&d_e, SM));
+    NMRFIT_HIP(hipMemcpyAsync(d_c, cand, 2 * SM * sizeof(double), hipMemcpyHostToDevice, st));
+    if (n_mean) {
+        NMRFIT_HIP(mem.alloc(&d_n, (size_t)S));
+        NMRFIT_HIP(hipMemcpyAsync(d_n, n_mean, (size_t)S * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    const dim3 grid((unsigned)M, (unsigned)S), block((unsigned)max_threads(off));
+    if (kind == NMRFIT_PHASE_ACME)
+        hipLaunchKernelGGL(phase_scores_kernel<kScoreAcme>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e, d_n);
+    else if (kind == NMRFIT_PHASE_PEAK_MINIMA)
+        hipLaunchKernelGGL(phase_scores_kernel<kScorePeakMinima>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e, d_n);
+    else
+        hipLaunchKernelGGL(phase_scores_kernel<kScoreBrute>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e, d_n);
+    NMRFIT_HIP(hipGetLastError());
+    NMRFIT_HIP(hipMemcpyAsync(score, d_s, SM * sizeof(double), hipMemcpyDeviceToHost, st));
+    NMRFIT_HIP(hipMemcpyAsync(empty, d_e, SM * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NMRFIT_HIP(hipStreamSynchronize(st));
+    return NMRFIT_OK;
+}
+
 }  // namespace
 }  // namespace nmrfit
 
@@ -594,42 +640,48 @@ int nmrfit_phase_scores(int device, int kind, int32_t S, const int64_t *N, const
     if (rc != NMRFIT_OK) return rc;
     if (kind == NMRFIT_PHASE_BRUTE_LEVEL)
         for (int32_t k = 0; k < S; ++k)
-            if (std::max<int64_t>(1, N[k] / 5000) > kBruteMaxMeanTerms) {
+            if (brute_default_mean(N[k]) > kBruteMaxMeanTerms) {
                 set_error(std::string(who) + ": the brute level test takes means of at most 128 points (N < 645000)");
                 return NMRFIT_E_UNSUPPORTED;
             }
-    if ((rc = check_device(device)) != NMRFIT_OK) return rc;
-    StreamLease lease(device);
-    NMRFIT_HIP(take_stream(device, &lease.s));
-    hipStream_t st = lease.s;
-    Scratch mem;
-    double *d_u = nullptr, *d_v = nullptr, *d_c = nullptr, *d_s = nullptr;
-    int64_t *d_off = nullptr;
-    int32_t *d_e = nullptr;
-    const size_t SM = (size_t)S * (size_t)M;
-    if ((rc = upload_spectra(st, mem, off, u, v, &d_u, &d_v, &d_off)) != NMRFIT_OK) return rc;
-    NMRFIT_HIP(mem.alloc(&d_c, 2 * SM));
-    NMRFIT_HIP(mem.alloc(&d_s, SM));
-    NMRFIT_HIP(mem.alloc(&d_e, SM));
-    NMRFIT_HIP(hipMemcpyAsync(d_c, cand, 2 * SM * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)M, (unsigned)S), block((unsigned)max_threads(off));
-    if (kind == NMRFIT_PHASE_ACME)
-        hipLaunchKernelGGL(phase_scores_kernel<kScoreAcme>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e);
-    else if (kind == NMRFIT_PHASE_PEAK_MINIMA)
-        hipLaunchKernelGGL(phase_scores_kernel<kScorePeakMinima>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e);
-    else
-        hipLaunchKernelGGL(phase_scores_kernel<kScoreBrute>, grid, block, 0, st, d_u, d_v, d_off, M, d_c, d_s, d_e);
-    NMRFIT_HIP(hipGetLastError());
-    std::vector<int32_t> empty(SM);
-    NMRFIT_HIP(hipMemcpyAsync(score, d_s, SM * sizeof(double), hipMemcpyDeviceToHost, st));
-    NMRFIT_HIP(hipMemcpyAsync(empty.data(), d_e, SM * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NMRFIT_HIP(hipStreamSynchronize(st));
+    std::vector<int32_t> empty((size_t)S * (size_t)M);
+    if ((rc = run_scores(device, kind, S, off, u, v, M, cand, nullptr, score, empty.data())) != NMRFIT_OK) return rc;
     for (int32_t k = 0; k < S; ++k) {
         status[k] = kStatusOk;
         for (int32_t m = 0; m < M; ++m)
             if (empty[(size_t)k * M + m]) status[k] = kStatusEmptyWindow;
     }
     return NMRFIT_OK;
+}
+
+int nmrfit_phase_brute_levels(int device, int32_t S, const int64_t *N, const int64_t *n_mean, const double *u,
+                              const double *v, int32_t M, const double *cand, double *score)
+{
+    const char *who = "nmrfit_phase_brute_levels";
+    if (M < 1) {
+        set_error(std::string(who) + ": M must be >= 1");
+        return NMRFIT_E_INVALID;
+    }
+    if (!n_mean || !cand || !score) {
+        set_error(std::string(who) + ": null pointer");
+        return NMRFIT_E_INVALID;
+    }
+    std::vector<int64_t> off;
+    int rc = check_spectra(who, S, N, u, v, &off);
+    if (rc != NMRFIT_OK) return rc;
+    for (int32_t k = 0; k < S; ++k) {
+        if (n_mean[k] < 1) {
+            set_error(std::string(who) + ": the mean length must be >= 1 (spectrum " + std::to_string(k) + ")");
+            return NMRFIT_E_INVALID;
+        }
+        if (n_mean[k] > kBruteMaxMeanTerms) {
+            set_error(std::string(who) + ": the brute level test takes means of at most 128 points, spectrum " +
+                      std::to_string(k) + " asks for a mean length of " + std::to_string(n_mean[k]));
+            return NMRFIT_E_UNSUPPORTED;
+        }
+    }
+    std::vector<int32_t> empty((size_t)S * (size_t)M);
+    return run_scores(device, NMRFIT_PHASE_BRUTE_LEVEL, S, off, u, v, M, cand, n_mean, score, empty.data());
 }
 
 int nmrfit_phase_estimate(int device, int kind, int32_t S, const int64_t *N, const double *u, const double *v,

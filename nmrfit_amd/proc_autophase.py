@@ -81,7 +81,7 @@ def approximate_phase(data, fn, p0=0.0, p1=0.0):
     return opt[0] * np.pi / 180, opt[1] * np.pi / 180
 
 
-# ---- device-batched phase estimation (opt-in; libnmrfit_amd.so: nmrfit_phase_scores / nmrfit_phase_estimate) ----------
+# ---- device-batched phase estimation (opt-in; libnmrfit_amd.so: nmrfit_phase_scores / _estimate / _brute_levels) ---
 # The functions above stay the host path Data.shift_phase runs.  These evaluate the same scores and run the same
 # scipy.optimize.fmin for a whole list of spectra of any lengths on the GPU: one workgroup per spectrum runs the whole
 # Nelder-Mead, each score a workgroup reduction.  Inputs are converted to float64: a complex64
@@ -210,19 +210,35 @@ def autops_many(spectra, fn='acme', p0=0.0, p1=0.0, device=0):
     return [ps(z, p0=opt[0], p1=opt[1]) for z, opt in zip(spectra, x)]
 
 
-def brute_levels(us, vs, angles, device=0):
+def brute_levels(us, vs, angles, device=0, n=None):
     """The level test of Data._brute_phase for every angle and spectrum: (S, M) errors, NaN where the rotated
     spectrum is not upright (max(V) <= |min(V)|).  The rotation factors are exp(1j * angle), built here as ps2 builds
     them.  The device rounds V = real(exp(1j angle) (u + 1j v)) as fma(c, u, -(s v)), which is how numpy's complex
     multiply rounds it when it runs its FMA loop (x86-64 with AVX2 or AVX-512: the errors are then the host loop's bit
-    for bit); a numpy without that loop rounds c u - s v and can differ in the last bit.  Spectra of 645000 points or
-    more are refused (NmrfitError, NMRFIT_E_UNSUPPORTED): their means would take numpy's recursive pairwise order,
-    which the device does not restate.  Any number of spectra (cut into calls of at most 65535)."""
+    for bit); a numpy without that loop rounds c u - s v and can differ in the last bit.
+
+    ``n``: the length of the two means, a scalar or one per spectrum; None takes max(1, N // 5000) from each spectrum's
+    length N.  The host loop takes n from len(self.V) before its scan, and select_bounds crops u, v but not V: on a
+    cropped Data that n is not N's (shift_phase_many passes the host's).  Where n > N the slices V[:n], V[-n:] are the
+    whole spectrum and the error is 0, as in python.  Mean lengths above 128 are refused (NmrfitError,
+    NMRFIT_E_UNSUPPORTED; by default spectra of 645000 points or more): those means would take numpy's recursive
+    pairwise order, which the device does not restate.  Any number of spectra (cut into calls of at most 65535)."""
+    from . import _cabi
     fac = np.exp(1j * np.asarray(angles, dtype=np.float64))
-    cand = np.empty((len(us), fac.size, 2), dtype=np.float64)
+    S = len(us)
+    cand = np.empty((S, fac.size, 2), dtype=np.float64)
     cand[:, :, 0] = fac.real
     cand[:, :, 1] = fac.imag
     N = np.array([len(u) for u in us], dtype=np.int64)
     u = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64) for a in us]))
     v = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64) for a in vs]))
-    return _device_scores(2, N, u, v, cand, device)[0]
+    if n is None:
+        n_mean = np.maximum(1, N // 5000)
+    else:
+        n_mean = np.ascontiguousarray(np.broadcast_to(np.asarray(n, dtype=np.int64), (S,)))
+    score = np.empty((S, fac.size), dtype=np.float64)
+    for k0, k1, o0, o1 in _chunks(N):
+        _cabi.check(_cabi.lib().nmrfit_phase_brute_levels(
+            int(device), k1 - k0, _cabi.ptr(N[k0:k1]), _cabi.ptr(n_mean[k0:k1]), _cabi.ptr(u[o0:o1]),
+            _cabi.ptr(v[o0:o1]), fac.size, _cabi.ptr(cand[k0:k1]), _cabi.ptr(score[k0:k1])))
+    return score
