@@ -320,6 +320,32 @@ int nmrfit_phase_estimate(int device, int kind, int32_t S, const int64_t *N, con
 int nmrfit_phase_brute_levels(int device, int32_t S, const int64_t *N, const int64_t *n_mean, const double *u,
                               const double *v, int32_t M, const double *cand, double *score);
 
+/* ---- automatic peak picking (opt-in: Data.select_peaks stays the reference's host path) ------------------------------
+ * Added within ABI 6 like the phase entry points (found by symbol lookup).  AutoPeakSelector(w, V, thresh, window)
+ * .find_peaks() of the reference (nmrfit/utils.py:670-783; Data.select_peaks, nmrfit/containers.py:132-173) for S
+ * spectra of any lengths, laid out one after the other as in nmrfit_batch_create_ragged.  Per spectrum k of N[k] >= 2
+ * points and M = 100 N[k] upsampled points:
+ *   w, u     the spectrum sorted by w ascending (the caller sorts, as interp1d does: argsort(kind='mergesort')); an
+ *            unsorted or NaN w is NMRFIT_E_INVALID
+ *   edges    10 doubles: savgol_filter(U, 11, 4)[:5] and [-5:] (scipy fits the ends with a polynomial; the caller
+ *            computes them from U[:11] and U[-11:], which give the full-length filter's values bit for bit)
+ *   order    int(window / (W[1] - W[0])) >= 1, the argrelmax half-window;  thresh  the height threshold
+ * The device computes W = np.linspace(w[0], w[N-1], M), U = interp1d(w, u)(W) (numpy.interp's arithmetic) and the interior
+ * of S = savgol_filter(U, 11, 4) bit for bit; the global baseline peakutils.baseline(S, 0)[0]; the strict maxima of S
+ * over +-order with U[i] - baseline > thresh; per maximum the half-height crossings nearest to it, width, bounds
+ * loc -+ 2 width, the index range of the bounds, the local baseline over that range and Simpson's area (scipy 1.15.3).
+ * The baselines' means and the area's sum are compensated sums in a fixed order that depends on the spectrum alone (not
+ * the host's BLAS order): a spectrum's results are bit-identical alone or in any batch.
+ * Outputs: baseline, count: S values.  Spectrum k's peaks fill the first count[k] records of its capacity
+ * cap_k = (M - 1) / (order[k] + 1) + 1 (two maxima are more than order apart), the capacities one after the other:
+ *   peak_idx  3 int64 per record: i (index into W), first and last index of the bounds (np.where of the reference)
+ *   peak_val  5 doubles per record: loc, width, local baseline, height (U[i] - local baseline), area
+ * Limits: 1 <= S <= 65535 per call; the M summed over a call at most 2^26 (the U and S workspace: 1 GiB), else
+ * NMRFIT_E_UNSUPPORTED (the Python layer cuts longer lists); order < 1, N < 2: NMRFIT_E_INVALID. */
+int nmrfit_peaks_pick(int device, int32_t S, const int64_t *N, const double *w, const double *u, const double *edges,
+                      const int64_t *order, const double *thresh, double *baseline, int64_t *count, int64_t *peak_idx,
+                      double *peak_val);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,12 @@ int nmrfit_batch_get_state(nmrfit_batch *batch, int32_t k, double *x, double *v,
 int nmrfit_diag_phase_nm_rosenbrock(int device, int32_t S, const double *x0, double *x, double *f, int32_t *nfev,
                                     int32_t *nit);
 
+/* ---- automatic peak picking: the upsampled and smoothed spectra ----------------------------------------------------
+ * Stage 1 of nmrfit_peaks_pick alone (same arguments): U = interp1d(w, u)(W) and S = savgol_filter(U, 11, 4) of every
+ * spectrum, 100 N[k] doubles each, one after the other -- what the tests compare with scipy bit for bit. */
+int nmrfit_diag_peaks_smooth(int device, int32_t S, const int64_t *N, const double *w, const double *u,
+                             const double *edges, double *U, double *Sm);
+
 #ifdef __cplusplus
 }
 #endif

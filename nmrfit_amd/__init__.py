@@ -10,15 +10,17 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.pso.DeviceSwarm / pso.pso                         (replaces pyswarm.pso)
     nmrfit_amd.Data(w, u, v)                                     (nmrfit/containers.py:8, scripted use)
     nmrfit_amd.shift_phase_many(datas, method='auto')            Data.shift_phase for many spectra: the phase search on the DEVICE
+    nmrfit_amd.select_peaks_many(datas, method='auto')           Data.select_peaks for many spectra: peak picking on the DEVICE
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
-there is no CPU fallback.  The automatic phase estimate runs on the device too when asked for by
-shift_phase_many / proc_autophase.approximate_phase_many (opt-in: Data.shift_phase stays the reference's host
-path).  The other once-per-dataset helpers (peak picking, bounds, weights) are host code as in the reference.  Instrument I/O (nmrfit.load), the
+there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
+asked for by shift_phase_many / proc_autophase.approximate_phase_many and select_peaks_many / peaks.find_peaks_many
+(opt-in: Data.shift_phase and Data.select_peaks stay the reference's host paths).  The other once-per-dataset helpers
+(bounds, weights) are host code as in the reference.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
 from . import batch, containers, equations, peaks, proc_autophase, pso, synth, utils  # noqa: F401
-from .containers import Data, shift_phase_many  # noqa: F401
+from .containers import Data, select_peaks_many, shift_phase_many  # noqa: F401
 
 __version__ = "0.1.0"

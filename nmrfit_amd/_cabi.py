@@ -135,6 +135,8 @@ ALL_SIGNATURES = {
     "nmrfit_phase_estimate": [_INT, _INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_phase_brute_levels": [_INT, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP],
     "nmrfit_diag_phase_nm_rosenbrock": [_INT, _I32, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_peaks_pick": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_diag_peaks_smooth": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
 }
 
 _DIAG_NAMES = (
@@ -144,7 +146,8 @@ _DIAG_NAMES = (
     "nmrfit_pso_set_fused_pbest", "nmrfit_pso_set_fused_tail", "nmrfit_pso_last_launches", "nmrfit_pso_get_state",
     "nmrfit_comm_describe", "nmrfit_comm_all_gather_dev", "nmrfit_comm_all_reduce_host", "nmrfit_comm_barrier",
     "nmrfit_diag_ab_build", "nmrfit_batch_step", "nmrfit_batch_synchronize", "nmrfit_batch_set_geometry",
-    "nmrfit_batch_geometry", "nmrfit_batch_get_state", "nmrfit_diag_phase_nm_rosenbrock")
+    "nmrfit_batch_geometry", "nmrfit_batch_get_state", "nmrfit_diag_phase_nm_rosenbrock",
+    "nmrfit_diag_peaks_smooth")
 DIAG_SIGNATURES = {k: ALL_SIGNATURES[k] for k in _DIAG_NAMES}
 SIGNATURES = {k: v for k, v in ALL_SIGNATURES.items() if k not in DIAG_SIGNATURES}
 

@@ -142,3 +142,23 @@ def shift_phase_many(datas, method='auto', p0=0.0, p1=0.0, step=np.pi / 360, dev
         d.p0, d.p1 = a, b
         d.V, d.I = proc_autophase.ps2(d.u, d.v, d.p0, d.p1)
     return datas
+
+
+def select_peaks_many(datas, method='auto', thresh=0.0, window=0.02, device=0):
+    """``for d in datas: d.select_peaks(method, thresh=thresh, window=window)`` with the picking of all of them on the
+    GPU (opt-in; Data.select_peaks stays the host path): peaks.find_peaks_many on every (d.w, d.V).  Sets ``peaks`` and
+    ``roibounds``.  ``thresh`` and ``window``: scalars or one value per object.  'manual' and unknown methods raise
+    what Data.select_peaks raises; a Data cropped by select_bounds and not re-phased (len(w) != len(V)) raises
+    ValueError, as interp1d does on the host.  Every error comes before any device work."""
+    datas = list(datas)
+    choice = method.lower()
+    if choice == 'manual':
+        raise ValueError("Number of peaks must be specified when using 'manual' flag")
+    if choice != 'auto':
+        raise ValueError("Method must be 'auto' or 'manual'.")
+    found = _peaks.find_peaks_many([d.w for d in datas], [d.V for d in datas], thresh=thresh, window=window,
+                                   device=device)
+    for d, p in zip(datas, found):
+        d.peaks = p
+        d.roibounds = [q.bounds for q in p]
+    return datas

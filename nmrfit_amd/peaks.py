@@ -181,3 +181,161 @@ def sample_noise(X, Y, xstart, xstop):
     sel = np.where((X <= xstop) & (X >= xstart))
     xs, ys = X[sel], Y[sel]
     return np.std(ys - np.poly1d(np.polyfit(xs, ys, 2))(xs))
+
+
+# ---- automatic peak picking on the GPU (opt-in; csrc/peaks.hip, nmrfit_peaks_pick) --------------------------------------
+
+UPSAMPLE = 100                     # AutoPeakSelector: np.linspace(w.min(), w.max(), len(w) * 100)
+POINT_BUDGET = 1 << 26             # upsampled points per library call: U and S take 16 bytes each point (1 GiB)
+_MAX_SPECTRA_PER_CALL = 65535      # the library's limit per call
+
+
+def grid_points(wmin, wmax, M, k):
+    """np.linspace(wmin, wmax, M)[k] for an integer array k, in numpy's arithmetic: k * step + wmin, the last point
+    wmax; a step that rounds to 0 takes (k / div) * delta."""
+    k = np.asarray(k, dtype=np.int64)
+    delta = np.float64(wmax) - np.float64(wmin)
+    div = M - 1
+    step = delta / div
+    kf = k.astype(np.float64)
+    W = (kf / div) * delta + wmin if step == 0 else kf * step + wmin
+    return np.where(k == M - 1, np.float64(wmax), W)
+
+
+def _prepare(w, u, window=None):
+    """Host side of one spectrum, with the host's exceptions: (xs, ys sorted by w, the 10 savgol edge values, order,
+    M).  order is None without a window."""
+    w = np.asarray(w, dtype=float)
+    u = np.asarray(u, dtype=float)
+    if w.ndim != 1 or u.ndim != 1 or len(w) != len(u):
+        raise ValueError("x and y arrays must be equal in length along interpolation axis.")
+    ind = np.argsort(w, kind="mergesort")          # interp1d's own sort
+    xs, ys = w[ind], u[ind]
+    M = int(len(w) * UPSAMPLE)
+    wmin, wmax = w.min(), w.max()
+    order = None
+    if window is not None:
+        W01 = grid_points(wmin, wmax, M, [0, 1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            order = int(window / (W01[1] - W01[0]))     # (N = 1: a zero step, OverflowError, as on the host)
+        if order < 1:
+            raise ValueError("Order must be an int >= 1")
+    if len(w) < 2:
+        raise ValueError("x and y arrays must have at least 2 entries")
+    head = np.interp(grid_points(wmin, wmax, M, np.arange(11)), xs, ys)
+    tail = np.interp(grid_points(wmin, wmax, M, np.arange(M - 11, M)), xs, ys)
+    edges = np.concatenate([scipy.signal.savgol_filter(head, 11, 4)[:5], scipy.signal.savgol_filter(tail, 11, 4)[-5:]])
+    return xs, ys, edges, order, M
+
+
+def _calls(Ms):
+    """[k0, k1) ranges of at most _MAX_SPECTRA_PER_CALL spectra and POINT_BUDGET upsampled points (a lone spectrum
+    above the budget is its own call; the library refuses it)."""
+    k0, n = 0, len(Ms)
+    while k0 < n:
+        k1, pts = k0, 0
+        while k1 < n and k1 - k0 < _MAX_SPECTRA_PER_CALL and (k1 == k0 or pts + Ms[k1] <= POINT_BUDGET):
+            pts += Ms[k1]
+            k1 += 1
+        yield k0, k1
+        k0 = k1
+
+
+def _per_spectrum(x, S, name):
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim == 0:
+        return [float(a)] * S
+    if a.shape != (S,):
+        raise ValueError("%s must be a scalar or one value per spectrum (%d), got shape %s" % (name, S, a.shape))
+    return list(a)
+
+
+def _device_smooth(prep, device=0):
+    """Stage 1 alone (nmrfit_diag_peaks_smooth): [(U, S)] of every prepared spectrum."""
+    from . import _cabi
+    out = []
+    for k0, k1 in _calls([p[4] for p in prep]):
+        part = prep[k0:k1]
+        N = np.array([len(p[0]) for p in part], dtype=np.int64)
+        xs = np.ascontiguousarray(np.concatenate([p[0] for p in part]))
+        ys = np.ascontiguousarray(np.concatenate([p[1] for p in part]))
+        edges = np.ascontiguousarray(np.concatenate([p[2] for p in part]))
+        tot = int(N.sum()) * UPSAMPLE
+        U = np.empty(tot)
+        Sm = np.empty(tot)
+        _cabi.check(_cabi.lib().nmrfit_diag_peaks_smooth(int(device), len(part), _cabi.ptr(N), _cabi.ptr(xs),
+                                                         _cabi.ptr(ys), _cabi.ptr(edges), _cabi.ptr(U), _cabi.ptr(Sm)))
+        o = 0
+        for p in part:
+            out.append((U[o:o + p[4]], Sm[o:o + p[4]]))
+            o += p[4]
+    return out
+
+
+def smooth_many(ws, us, device=0):
+    """The device's upsampled and smoothed spectra: [(U, S)] with U = interp1d(w, u)(W) on the 100x grid and
+    S = savgol_filter(U, 11, 4), bit for bit (what AutoPeakSelector holds as ``u`` and ``u_smoothed``)."""
+    ws, us = list(ws), list(us)
+    if len(ws) != len(us):
+        raise ValueError("ws and us differ in length")
+    return _device_smooth([_prepare(w, u) for w, u in zip(ws, us)], device)
+
+
+def capacity(M, order):
+    """The most maxima a spectrum of M upsampled points can have over +-order: two are more than order apart."""
+    return (M - 1) // (order + 1) + 1
+
+
+def find_peaks_many(ws, us, thresh=0.0, window=0.02, device=0, return_baseline=False):
+    """``AutoPeakSelector(w, u, thresh, window).find_peaks()`` for every (w, u), on the GPU (opt-in; csrc/peaks.hip).
+    Returns a list of ``Peaks`` (and, with ``return_baseline``, the array of global baselines, the host's
+    ``selector.baseline``).  ``thresh`` and ``window``: scalars or one value per spectrum.  Spectra may differ in
+    length; lists of any length are cut into library calls of at most 65535 spectra and POINT_BUDGET (2^26) upsampled
+    points.  Count, i, loc, width, bounds and idx are the host's exactly; the global and local baselines, height and area
+    agree with the host to about 1e-14 relative (the host's means take BLAS's order, the device a compensated sum of its
+    own).  Argument errors raise the host's exceptions before any device work."""
+    from . import _cabi
+    ws, us = list(ws), list(us)
+    if len(ws) != len(us):
+        raise ValueError("ws and us differ in length")
+    S = len(ws)
+    th = _per_spectrum(thresh, S, "thresh")
+    wi = _per_spectrum(window, S, "window")
+    prep = [_prepare(w, u, win) for w, u, win in zip(ws, us, wi)]
+    result, base_all = [], np.empty(S)
+    for k0, k1 in _calls([p[4] for p in prep]):
+        part = prep[k0:k1]
+        n = len(part)
+        N = np.array([len(p[0]) for p in part], dtype=np.int64)
+        xs = np.ascontiguousarray(np.concatenate([p[0] for p in part]))
+        ys = np.ascontiguousarray(np.concatenate([p[1] for p in part]))
+        edges = np.ascontiguousarray(np.concatenate([p[2] for p in part]))
+        order = np.array([p[3] for p in part], dtype=np.int64)
+        th_arr = np.array(th[k0:k1], dtype=np.float64)
+        cap = np.array([capacity(p[4], p[3]) for p in part], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(cap)])
+        base = np.empty(n)
+        count = np.zeros(n, dtype=np.int64)
+        pidx = np.empty((int(off[-1]), 3), dtype=np.int64)
+        pval = np.empty((int(off[-1]), 5), dtype=np.float64)
+        _cabi.check(_cabi.lib().nmrfit_peaks_pick(
+            int(device), n, _cabi.ptr(N), _cabi.ptr(xs), _cabi.ptr(ys), _cabi.ptr(edges), _cabi.ptr(order),
+            _cabi.ptr(th_arr), _cabi.ptr(base), _cabi.ptr(count), _cabi.ptr(pidx), _cabi.ptr(pval)))
+        base_all[k0:k1] = base
+        for k in range(n):
+            out = Peaks()
+            for r in range(int(off[k]), int(off[k]) + int(count[k])):
+                i, lo, hi = pidx[r]
+                loc, width, pb, height, area = pval[r]
+                p = Peak()
+                p.loc = np.float64(loc)
+                p.i = np.int64(i)
+                p.width = np.float64(width)
+                p.bounds = [p.loc - 2 * p.width, p.loc + 2 * p.width]
+                p.idx = (np.arange(lo, hi + 1, dtype=np.int64),)
+                p.baseline = np.float64(pb)
+                p.height = np.float64(height)
+                p.area = np.float64(area)
+                out.append(p)
+            result.append(out)
+    return (result, base_all) if return_baseline else result
