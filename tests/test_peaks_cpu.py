@@ -7,6 +7,7 @@ import ctypes
 import os
 import re
 import subprocess
+import warnings
 
 import numpy as np
 import pytest
@@ -15,94 +16,9 @@ import scipy.interpolate
 import scipy.signal
 
 from nmrfit_amd import _cabi, containers, peaks, synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "nmrfit_amd", "csrc", "peaks.hip")
-
-
-# ---- the device's steps, restated in numpy (the order of every exact operation is peaks.hip's) ------------------------
-
-def interp_np(xs, ys, W):
-    """numpy.interp's arithmetic (csrc/peaks.hip: interp_at)."""
-    N = len(xs)
-    j = np.searchsorted(xs, W, side="right") - 1
-    j = np.clip(j, 0, N - 1)
-    jj = np.minimum(j, N - 2)
-    with np.errstate(all="ignore"):
-        slope = (ys[jj + 1] - ys[jj]) / (xs[jj + 1] - xs[jj])
-        r = slope * (W - xs[jj]) + ys[jj]
-        bad = np.isnan(r)
-        r2 = slope * (W - xs[jj + 1]) + ys[jj + 1]
-        r = np.where(bad, r2, r)
-        r = np.where(np.isnan(r) & bad & (ys[jj] == ys[jj + 1]), ys[jj], r)
-    r = np.where(xs[j] == W, ys[j], r)
-    return np.where(j == N - 1, ys[N - 1], r)
-
-
-def savgol_np(U, edges):
-    c = [float.fromhex(h) for h in _hip_savgol()]
-    S = U[5:-5] * c[0]
-    for k in (5, 4, 3, 2, 1):
-        S = S + (U[5 + k:len(U) - 5 + k] + U[5 - k:len(U) - 5 - k]) * c[k]
-    return np.concatenate([edges[:5], S, edges[5:]])
-
-
-def const_baseline_np(y, mean=lambda a: np.float64(__import__("math").fsum(a)) / len(a)):
-    """peakutils.baseline(y, 0)[0] with the device's quirks: the last accepted c, y[0] on a first-test pass."""
-    coef, clip, out = 1.0, np.inf, y[0]
-    for _ in range(100):
-        with np.errstate(all="ignore"):
-            m = mean(np.minimum(y, clip))
-            d = m - coef
-            if np.sqrt(d * d) / np.sqrt(coef * coef) < 1e-3:
-                break
-        coef = out = m
-        clip = np.minimum(clip, m)
-    return out
-
-
-def nearest(cands, W, loc):
-    if cands.size == 0:
-        return None
-    d = np.abs(W[cands] - loc)
-    return cands[np.argmin(d)]
-
-
-def emulate(w, u, thresh, window):
-    """(peak dicts, global baseline) by the device's plan, the means by math.fsum."""
-    xs, ys, edges, order, M = peaks._prepare(w, u, window)
-    W = peaks.grid_points(xs[0], xs[-1], M, np.arange(M))
-    U = interp_np(xs, ys, W)
-    S = savgol_np(U, edges)
-    B = const_baseline_np(S)
-    out = []
-    for i in peaks.argrelmax(S, order):
-        h = U[i] - B
-        if not h > thresh:
-            continue
-        with np.errstate(all="ignore"):
-            side = np.sign(h / 2.0 - (U - B))
-        cr = side[:-1] - side[1:]
-        jf, jr = nearest(np.flatnonzero(cr < 0), W, W[i]), nearest(np.flatnonzero(cr > 0), W, W[i])
-        if jf is None or jr is None or not W[jr] < W[jf]:
-            continue
-        width = W[jf] - W[jr]
-        b = [W[i] - 2 * width, W[i] + 2 * width]
-        sel = np.flatnonzero((W >= b[0]) & (W <= b[1]))
-        pb = const_baseline_np(U[sel])
-        out.append(dict(i=i, loc=W[i], width=width, bounds=b, lo=sel[0], hi=sel[-1], baseline=pb, height=U[i] - pb,
-                        area=scipy.integrate.simpson(U[sel] - pb, x=W[sel])))
-    return out, B, U, S
-
-
-def _hip_savgol():
-    text = open(SRC).read()
-    body = re.search(r"kSavgol\[6\]\s*=\s*\{([^}]*)\}", text).group(1)
-    return [t.strip() for t in body.split(",")]
-
-
-def close(a, b, scale, rel=1e-12):
-    return abs(a - b) <= rel * max(abs(b), scale)
+from tests import peaks_support
+from tests.peaks_support import (ROOT, SRC, _hip_savgol, close, const_baseline_np, emulate, interp_np,  # noqa: F401
+                                 nearest, savgol_np)
 
 
 # ---- tests -------------------------------------------------------------------------------------------------------------
@@ -175,7 +91,7 @@ def test_restated_plan_matches_the_host_mirror(N, P, descending):
         w, u = w[::-1].copy(), u[::-1].copy()
     sel = peaks.AutoPeakSelector(w, u, 0.1, 0.02)
     sel.find_peaks()
-    got, B, U, S = emulate(w, u, 0.1, 0.02)
+    got, B, U, S = emulate(w, u, 0.1, 0.02)[:4]
     scale = np.abs(U).max()
     assert close(B, sel.baseline, scale)
     assert len(got) == len(sel.peaks) > 0
@@ -184,6 +100,166 @@ def test_restated_plan_matches_the_host_mirror(N, P, descending):
         assert np.array_equal(np.arange(g["lo"], g["hi"] + 1), p.idx[0])
         assert close(g["baseline"], p.baseline, scale) and close(g["height"], p.height, scale)
         assert close(g["area"], p.area, scale * p.width)
+
+
+# ---- the exactly summed truth and the edge cases of tests/test_gpu_peaks_edges.py -------------------------------------------
+
+def test_restated_simpson_is_scipys():
+    """The term-by-term Simpson, summed exactly, against scipy.integrate.simpson (which sums with np.sum): within a few
+    ulp of the sum of the |terms|, on odd, even, 3-point, 2-point and duplicate-abscissa inputs."""
+    rng = np.random.default_rng(21)
+    inputs = []
+    for n in (3, 4, 5, 6, 101, 256, 1001):
+        inputs.append((rng.standard_normal(n), np.sort(rng.uniform(0.0, 3.0, n))))
+        inputs.append((rng.standard_normal(n), np.linspace(2.0, 3.0, n)))
+    inputs.append((np.array([1.0, 3.0]), np.array([0.5, 0.75])))
+    for n in (5, 6, 9, 10):                       # coincident neighbours: the where= guards
+        x = np.sort(rng.uniform(0.0, 1.0, n))
+        for k in range(1, n, 3):
+            x[k] = x[k - 1]
+        inputs.append((rng.standard_normal(n), x))
+    inputs.append((rng.standard_normal(6), np.array([0.0, 1.0, 2.0, 3.0, 3.0, 3.0])))      # den == 0 in the correction
+    inputs.append((rng.standard_normal(6), np.array([0.0, 1.0, 2.0, 3.0, 3.0, 4.0])))
+    for y, x in inputs:
+        st = peaks_support.simpson_terms(y, x)
+        ref = scipy.integrate.simpson(y, x=x)
+        assert len(st.corr) == (3 if len(y) % 2 == 0 and len(y) > 2 else 0)
+        assert abs(peaks_support.simpson_exact(st) - ref) <= 8 * peaks_support.EPS * st.mag, (len(y), x[:6])
+
+
+def test_sum_bound_separates_a_compensated_sum_from_a_plain_one():
+    """A long local range with cancellation: the plain left-to-right float64 sum misses the exact sum by more than
+    sum_bound, the model of the device's lane-strided Neumaier sum stays inside."""
+    rng = np.random.default_rng(4)
+    x = rng.standard_normal(20000) * 10.0 ** rng.uniform(-3, 3, 20000)
+    x = np.concatenate([x, -x[::-1] * (1.0 + 1e-9)])          # cancels to 1e-9 of its magnitude
+    exact = peaks_support.exact_sum(x)
+    for lanes in (peaks_support.LOCAL_LANES, peaks_support.GLOBAL_LANES):
+        bound = peaks_support.sum_bound(x, lanes)
+        assert abs(peaks_support.plain_sum(x) - exact) > bound
+        assert abs(float(np.sum(x)) - exact) > bound                                      # numpy's pairwise sum too
+        assert abs(peaks_support.neumaier_lanes(x, lanes) - exact) <= bound
+    # without cancellation a plain sum of 6.5 M positive terms is outside as well (the large GPU case's global mean)
+    y = rng.uniform(0.5, 1.5, 1 << 18)
+    assert abs(peaks_support.plain_sum(y) - peaks_support.exact_sum(y)) > peaks_support.sum_bound(y, 1024)
+    assert abs(peaks_support.neumaier_lanes(y, 1024) - peaks_support.exact_sum(y)) <= peaks_support.sum_bound(y, 1024)
+    with pytest.raises(ValueError):
+        peaks_support.sum_bound(np.ones(1 << 20), lanes=64)                               # outside the derivation's range
+
+
+def test_margin_ok_is_about_the_tolerance_alone():
+    T = peaks_support.Trace
+    assert peaks_support.margin_ok(T([0.5, 2e-3, 9e-4], 2, 0.0))
+    assert not peaks_support.margin_ok(T([0.5, 1e-3 * (1 + 1e-10)], 1, 0.0))
+    assert not peaks_support.margin_ok(T([0.5, 1e-3 * (1 - 1e-10)], 1, 0.0))
+    assert peaks_support.margin_ok(T([np.inf, np.nan], 2, 0.0))
+
+
+_EMULATED = {}
+
+
+def emulated(case):
+    """(inputs, exact truth, host mirror) of a case at its CPU size, computed once."""
+    if case.name not in _EMULATED:
+        w, u, thresh, window = peaks_support.case_inputs(case, cpu=True)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            em = emulate(w, u, thresh, window)
+            sel = peaks.AutoPeakSelector(w, u, thresh, window)
+            sel.find_peaks()
+        _EMULATED[case.name] = ((w, u, thresh, window), em, sel)
+    return _EMULATED[case.name]
+
+
+ALL_CASES = peaks_support.CASES + [peaks_support.LARGE]
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=lambda c: c.name)
+def test_edge_case_reaches_its_path_with_margin(case):
+    (w, u, thresh, window), em, sel = emulated(case)
+    for tag in case.tags:
+        assert peaks_support.reaches(tag, em, case), tag
+    assert peaks_support.margin_ok(em.trace)
+    for p in em.peaks:
+        assert peaks_support.margin_ok(p["trace"]), p["i"]
+    assert peaks_support.thresh_margin_ok(em, thresh)
+    if case.order is not None:
+        assert em.order == case.order
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=lambda c: c.name)
+def test_edge_case_restatement_matches_the_host_mirror(case):
+    """Count, i, loc, width, bounds and idx exactly; the sums under the 1e-12 contract, except where the HOST is the
+    inaccurate side (host_sums=False: the subnormal spectrum, where pinv's 1/n times a subnormal costs the host 1e-10 of
+    max|U|; shown here, and compared with the exact sums only on the GPU)."""
+    (w, u, thresh, window), em, sel = emulated(case)
+    assert len(em.peaks) == len(sel.peaks)
+    finite = np.isfinite(em.U).all()
+    scale = np.abs(em.U).max() if finite else 1.0
+    if finite:
+        ok_B = close(em.B, sel.baseline, scale)
+    else:
+        ok_B = (np.isnan(em.B) and np.isnan(sel.baseline)) or em.B == sel.baseline
+    ok = [ok_B]
+    for g, p in zip(em.peaks, sel.peaks):
+        assert g["i"] == p.i and g["loc"] == p.loc and g["width"] == p.width and g["bounds"] == p.bounds
+        assert np.array_equal(np.arange(g["lo"], g["hi"] + 1), p.idx[0]) and g["n"] == p.idx[0].size
+        ok += [close(g["baseline"], p.baseline, scale), close(g["height"], p.height, scale),
+               close(g["area"], p.area, scale * (p.bounds[1] - p.bounds[0]))]
+    if case.host_sums:
+        assert all(ok)
+    else:
+        assert not all(ok), "the host is accurate here after all: drop host_sums=False"
+        assert 0 < scale < np.finfo(np.float64).tiny
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=lambda c: c.name)
+def test_edge_case_device_sum_model_stays_inside_the_bounds(case):
+    """The same plan with every sum taken by the numpy model of the device's lane-strided Neumaier sum: the exact
+    fields do not move, and baseline, height and area stay inside the bounds the GPU tier holds the device to."""
+    (w, u, thresh, window), em, sel = emulated(case)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        lanes = {}
+
+        def model(a):                        # (the global baseline sums over 1024 lanes, everything else over 64)
+            return peaks_support.neumaier_lanes(a, lanes.get("n", peaks_support.LOCAL_LANES))
+        lanes["n"] = peaks_support.GLOBAL_LANES
+        B = peaks_support.const_baseline_trace(em.S, model, peaks_support.GLOBAL_LANES)[0]
+        lanes["n"] = peaks_support.LOCAL_LANES
+    if not np.isfinite(em.B):
+        assert (np.isnan(B) and np.isnan(em.B)) or B == em.B
+        return
+    assert abs(B - em.B) <= em.trace.err
+    for p in em.peaks:
+        y = em.U[p["lo"]:p["hi"] + 1]
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            pb = peaks_support.const_baseline_trace(y, model)[0]
+            st = peaks_support.simpson_terms(y - pb, em.W[p["lo"]:p["hi"] + 1])
+            area = peaks_support._device_simpson(st, model)
+        assert abs(pb - p["baseline"]) <= p["base_err"]
+        assert abs((em.U[p["i"]] - pb) - p["height"]) <= p["height_err"]
+        assert abs(area - p["area"]) <= p["area_err"]
+
+
+def test_stage_one_on_awkward_axes_restated_bit_for_bit():
+    for name, w, u in peaks_support.smooth_cases():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            xs, ys, edges, order, M = peaks._prepare(w, u)
+            W = peaks.grid_points(xs[0], xs[-1], M, np.arange(M))
+            ref_W = np.linspace(np.asarray(w, dtype=float).min(), np.asarray(w, dtype=float).max(), M)
+            assert np.array_equal(W, ref_W), name
+            ref_U = scipy.interpolate.interp1d(np.asarray(w, dtype=float), np.asarray(u, dtype=float))(ref_W)
+            ref_S = scipy.signal.savgol_filter(ref_U, 11, 4)
+            U = interp_np(xs, ys, W)
+        assert np.array_equal(U, ref_U, equal_nan=True), name
+        assert np.array_equal(savgol_np(U, edges), ref_S, equal_nan=True), name
+    # the zero-step branch of the grid is reached by two of them
+    assert peaks_support.grid_step(np.full(4, 2.5)) == 0.0 and peaks_support.grid_step(np.array([0.0, 5e-324])) == 0.0
+    with pytest.raises(OverflowError):
+        peaks._prepare(np.full(4, 2.5), np.ones(4), 0.02)
 
 
 def test_capacity_bounds_the_maxima():
