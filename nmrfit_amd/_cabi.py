@@ -27,6 +27,7 @@ VARIANT_FARFIELD32 = 8     # opt-in mixed precision: the far-field kernel's shar
 HANDOVER_FAST, HANDOVER_FENCED, HANDOVER_TWO_LAUNCH = 0, 1, 2
 ABI_VERSION = 6
 PHASE_ACME, PHASE_PEAK_MINIMA, PHASE_BRUTE_LEVEL = 0, 1, 2
+_MAX_SPECTRA_PER_CALL = 65535     # the library's limit per call (a launch's grid.y / grid.x): larger lists are cut
 _VARIANT_NAMES = {"default": 0, "baseline": 1, "noskip": 2, "single": 3, "quad": 4, "staged": 5, "farfield": 6,
                   "norec": 7, "farfield32": 8}
 

@@ -16,6 +16,7 @@
 // which from one of 8 + 1 descriptor tables built once at creation (phase of x / p, phase of the state block, fold
 // pending or not; + plain evaluation), so a generation costs the host one launch and no copies.
 #include "batch_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 #include "result_internal.h"
 
@@ -320,16 +321,6 @@ struct FitMem {
     double *lb, *ub, *x, *vel, *x2, *vel2, *p, *p_alt, *fx, *cand, *best, *best_alt;
 };
 
-struct Carver {
-    size_t total = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
 }  // namespace
 
 // ---- one part of a batch: a set of fits advanced by one launch per generation on one stream ----------------
@@ -367,24 +358,9 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
         set_error("nmrfit_batch_create: more than 65535 fits in one part");
         return NMRFIT_E_INVALID;
     }
-    int n = 0;
-    int rc = nmrfit_device_count(&n);
-    if (rc != NMRFIT_OK) return rc;
-    if (n == 0) {
-        set_error("no HIP device visible: libnmrfit_amd has no CPU fallback");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    NMRFIT_HIP(hipSetDevice(device));
     DeviceInfo prop;
-    if ((rc = device_info_cached(device, &prop)) != NMRFIT_OK) return rc;
-    if (strncmp(prop.arch, "gfx950", 6) != 0) {
-        set_error(std::string("device is ") + prop.arch + ", this library is built for gfx950 only");
-        return NMRFIT_E_NO_DEVICE;
-    }
+    int rc = use_device(device, &prop);
+    if (rc != NMRFIT_OK) return rc;
     BatchPart *b = new (std::nothrow) BatchPart();
     if (!b) {
         set_error("out of host memory");
@@ -433,16 +409,7 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
             delete b;
             return NMRFIT_E_INVALID;
         }
-#define BATCH_HIP(call)                                                \
-    do {                                                               \
-        hipError_t _e = (call);                                        \
-        if (_e != hipSuccess) {                                        \
-            int _rc = hip_fail(_e, #call, __FILE__, __LINE__);         \
-            part_destroy(b);                                   \
-            return _rc;                                                \
-        }                                                              \
-    } while (0)
-    BATCH_HIP(take_stream(device, &b->stream));
+    NMRFIT_HIP_OR(take_stream(device, &b->stream), part_destroy(b));
     plan_geometry(b);
     if (!b->geom_ok[0] && !b->geom_ok[1]) {
         set_error(b->N == 0 && b->fit_im == NMRFIT_FIT_IM_OFF
@@ -481,9 +448,10 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
     const size_t o_bestx = c.take((size_t)b->Dsum * sizeof(double) + (size_t)K * sizeof(int64_t));
     const size_t o_tables = c.take((size_t)9 * (size_t)K * sizeof(BatchFit));
     const size_t o_raw = c.take((size_t)4 * (size_t)Nsum * sizeof(double));
-    BATCH_HIP(hipMalloc(&b->d_block, c.total));
+    NMRFIT_HIP_OR(hipMalloc(&b->d_block, c.total), part_destroy(b));
     unsigned char *base = reinterpret_cast<unsigned char *>(b->d_block);
-    BATCH_HIP(hipMemsetAsync(base, 0, grid_state_end, b->stream));   // padding of the grid arrays (weight 0), state blocks
+    // padding of the grid arrays (weight 0), state blocks
+    NMRFIT_HIP_OR(hipMemsetAsync(base, 0, grid_state_end, b->stream), part_destroy(b));
     b->d_summary = reinterpret_cast<double *>(base + o_summary);
     b->d_bestx = reinterpret_cast<double *>(base + o_bestx);
     b->d_tables = reinterpret_cast<BatchFit *>(base + o_tables);
@@ -590,28 +558,32 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
     for (int t = 0; t < 8; ++t)
         for (int32_t k = 0; k < K; ++k) tabs[(size_t)t * (size_t)K + (size_t)k].upd.xrow_off = xrow_offset(b, b->mode);
     b->h_fits.assign(tabs.begin(), tabs.begin() + K);
-    BATCH_HIP(hipMemcpyAsync(b->d_tables, tabs.data(), tabs.size() * sizeof(BatchFit), hipMemcpyHostToDevice, b->stream));
-    BATCH_HIP(hipMemcpyAsync(b->d_bestx + b->Dsum, b->boff.data(), (size_t)K * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
+    NMRFIT_HIP_OR(hipMemcpyAsync(b->d_tables, tabs.data(), tabs.size() * sizeof(BatchFit), hipMemcpyHostToDevice, b->stream),
+                  part_destroy(b));
+    NMRFIT_HIP_OR(hipMemcpyAsync(b->d_bestx + b->Dsum, b->boff.data(), (size_t)K * sizeof(int64_t), hipMemcpyHostToDevice, b->stream),
+                  part_destroy(b));
     // ---- spectra: four uploads, one scatter kernel, one chunk-table kernel
     const size_t plane = (size_t)Nsum * sizeof(double);
     const double *host_arrays[] = {w, u, v, weights};
     for (int a = 0; a < 4; ++a)
-        BATCH_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char *>(d_raw) + (size_t)a * plane, host_arrays[a], plane,
-                                 hipMemcpyHostToDevice, b->stream));
-    BATCH_HIP(hipMemcpyAsync(base + o_lball, lower, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    BATCH_HIP(hipMemcpyAsync(base + o_uball, upper, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        NMRFIT_HIP_OR(hipMemcpyAsync(reinterpret_cast<unsigned char *>(d_raw) + (size_t)a * plane, host_arrays[a], plane,
+                                     hipMemcpyHostToDevice, b->stream),
+                      part_destroy(b));
+    NMRFIT_HIP_OR(hipMemcpyAsync(base + o_lball, lower, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream),
+                  part_destroy(b));
+    NMRFIT_HIP_OR(hipMemcpyAsync(base + o_uball, upper, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream),
+                  part_destroy(b));
     {
         PrepareArgs a{};
         a.plane = Nsum;
         a.raw = d_raw;
         a.fits = b->d_tables;
         hipLaunchKernelGGL(batch_prepare_kernel, dim3((unsigned)((b->Nmax + 255) / 256), (unsigned)K), dim3(256), 0, b->stream, a);
-        BATCH_HIP(hipGetLastError());
+        NMRFIT_HIP_OR(hipGetLastError(), part_destroy(b));
         hipLaunchKernelGGL(batch_chunk_minmax_kernel, dim3((unsigned)((b->n_chunks + 3) / 4), (unsigned)K), dim3(kWave * 4), 0, b->stream, a);
-        BATCH_HIP(hipGetLastError());
+        NMRFIT_HIP_OR(hipGetLastError(), part_destroy(b));
     }
-    BATCH_HIP(hipStreamSynchronize(b->stream));   // (the host vectors go out of scope)
-#undef BATCH_HIP
+    NMRFIT_HIP_OR(hipStreamSynchronize(b->stream), part_destroy(b));   // (the host vectors go out of scope)
     *out = b;
     return NMRFIT_OK;
 }

@@ -1,7 +1,7 @@
 // cabi.hip -- the extern "C" surface of libnmrfit_amd.so (include/nmrfit_amd.h): context
 // life-cycle, host-pointer and device-pointer forms of the objective / residual calls,
 // device memory and HIP-event timing helpers.  No exception leaves this file.
-#include "nmrfit_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 #include "result_internal.h"
 
@@ -195,6 +195,39 @@ int device_info_cached(int device, DeviceInfo *out)
     return NMRFIT_OK;
 }
 
+int use_device(int device, DeviceInfo *info)
+{
+    int n = 0;
+    int rc = nmrfit_device_count(&n);
+    if (rc != NMRFIT_OK) return rc;
+    if (n == 0) {
+        set_error("no HIP device visible: libnmrfit_amd has no CPU fallback");
+        return NMRFIT_E_NO_DEVICE;
+    }
+    if (device < 0 || device >= n) {
+        set_error("device index out of range");
+        return NMRFIT_E_NO_DEVICE;
+    }
+    NMRFIT_HIP(hipSetDevice(device));
+    DeviceInfo prop;
+    if ((rc = device_info_cached(device, &prop)) != NMRFIT_OK) return rc;
+    if (strncmp(prop.arch, "gfx950", 6) != 0) {
+        set_error(std::string("device is ") + prop.arch + ", this library is built for gfx950 only");
+        return NMRFIT_E_NO_DEVICE;
+    }
+    if (info) *info = prop;
+    return NMRFIT_OK;
+}
+
+int check_spectra_count(const char *who, int32_t S)
+{
+    if (S < 1 || S > 65535) {
+        set_error(std::string(who) + ": S must be 1..65535");
+        return NMRFIT_E_INVALID;
+    }
+    return NMRFIT_OK;
+}
+
 static int bind(const nmrfit_ctx *ctx)
 {
     if (!ctx) {
@@ -313,24 +346,9 @@ int nmrfit_ctx_create(int device, int64_t N, const double *w, const double *u, c
         set_error("nmrfit_ctx_create: N must be > 0 and w, u, v, weights non-null");
         return NMRFIT_E_INVALID;
     }
-    int n = 0;
-    int rc = nmrfit_device_count(&n);
-    if (rc != NMRFIT_OK) return rc;
-    if (n == 0) {
-        set_error("no HIP device visible: libnmrfit_amd has no CPU fallback");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    NMRFIT_HIP(hipSetDevice(device));
     DeviceInfo prop;
-    if ((rc = device_info_cached(device, &prop)) != NMRFIT_OK) return rc;
-    if (strncmp(prop.arch, "gfx950", 6) != 0) {
-        set_error(std::string("device is ") + prop.arch + ", this library is built for gfx950 only");
-        return NMRFIT_E_NO_DEVICE;
-    }
+    int rc = use_device(device, &prop);
+    if (rc != NMRFIT_OK) return rc;
     nmrfit_ctx *ctx = new (std::nothrow) nmrfit_ctx();
     if (!ctx) {
         set_error("out of host memory");
@@ -356,51 +374,40 @@ int nmrfit_ctx_create(int device, int64_t N, const double *w, const double *u, c
     analyse_grid(w, N, &ctx->w0, &ctx->wspan, &ctx->lane_step, &ctx->grid_dev);
     const size_t bytes = (size_t)N * sizeof(double);
     const size_t padded = (size_t)ctx->n_chunks * kChunk * sizeof(double);   // whole chunks, grid_slot order
-    double *d_w_raw = nullptr;
-#define CTX_HIP(call)                                                              \
-    do {                                                                           \
-        hipError_t _e = (call);                                                    \
-        if (_e != hipSuccess) {                                                    \
-            int _rc = hip_fail(_e, #call, __FILE__, __LINE__);                     \
-            nmrfit_ctx_destroy(ctx);                                               \
-            return _rc;                                                            \
-        }                                                                          \
-    } while (0)
-    CTX_HIP(take_stream(device, &ctx->own_stream));
+    NMRFIT_HIP_OR(take_stream(device, &ctx->own_stream), nmrfit_ctx_destroy(ctx));
     ctx->stream = ctx->own_stream;
-    CTX_HIP(hipEventCreate(&ctx->ev0));
-    CTX_HIP(hipEventCreate(&ctx->ev1));
+    NMRFIT_HIP_OR(hipEventCreate(&ctx->ev0), nmrfit_ctx_destroy(ctx));
+    NMRFIT_HIP_OR(hipEventCreate(&ctx->ev1), nmrfit_ctx_destroy(ctx));
     // ONE allocation for the four padded grid arrays, the chunk table and the landing buffer (which first holds the raw w)
-    const size_t chunk_bytes = ((size_t)ctx->n_chunks * sizeof(double2) + 255) & ~(size_t)255;
-    const size_t padded_al = (padded + 255) & ~(size_t)255;
-    CTX_HIP(hipMalloc((void **)&ctx->d_block, 4 * padded_al + chunk_bytes + bytes));
-    CTX_HIP(hipMemsetAsync(ctx->d_block, 0, 4 * padded_al, ctx->stream));
-    {
-        unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_block);
-        ctx->d_wc = reinterpret_cast<double *>(base);
-        ctx->d_u = reinterpret_cast<double *>(base + padded_al);
-        ctx->d_v = reinterpret_cast<double *>(base + 2 * padded_al);
-        ctx->d_wt = reinterpret_cast<double *>(base + 3 * padded_al);
-        ctx->d_chunk = reinterpret_cast<double2 *>(base + 4 * padded_al);
-        ctx->d_stage = reinterpret_cast<double *>(base + 4 * padded_al + chunk_bytes);
-    }
-    d_w_raw = ctx->d_stage;
-    CTX_HIP(hipMemcpyAsync(d_w_raw, w, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = prepare_grid(ctx, d_w_raw);
+    Carver c;
+    const size_t o_wc = c.take(padded), o_u = c.take(padded), o_v = c.take(padded), o_wt = c.take(padded);
+    const size_t o_chunk = c.take((size_t)ctx->n_chunks * sizeof(double2)), o_stage = c.take(bytes);
+    NMRFIT_HIP_OR(hipMalloc((void **)&ctx->d_block, c.total), nmrfit_ctx_destroy(ctx));
+    // (the four grid arrays: their padding is zeros, weight 0)
+    NMRFIT_HIP_OR(hipMemsetAsync(ctx->d_block, 0, o_chunk, ctx->stream), nmrfit_ctx_destroy(ctx));
+    unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_block);
+    ctx->d_wc = reinterpret_cast<double *>(base + o_wc);
+    ctx->d_u = reinterpret_cast<double *>(base + o_u);
+    ctx->d_v = reinterpret_cast<double *>(base + o_v);
+    ctx->d_wt = reinterpret_cast<double *>(base + o_wt);
+    ctx->d_chunk = reinterpret_cast<double2 *>(base + o_chunk);
+    ctx->d_stage = reinterpret_cast<double *>(base + o_stage);
+    NMRFIT_HIP_OR(hipMemcpyAsync(ctx->d_stage, w, bytes, hipMemcpyHostToDevice, ctx->stream), nmrfit_ctx_destroy(ctx));
+    rc = prepare_grid(ctx, ctx->d_stage);
     // u, v, weights: land in plain order, then into the pair-interleaved order the kernels read (nmrfit_internal.h,
     // grid_slot); stream order lets the one landing buffer serve all three
     const double *host_arrays[] = {u, v, weights};
     double *dev_arrays[] = {ctx->d_u, ctx->d_v, ctx->d_wt};
     for (int a = 0; a < 3 && rc == NMRFIT_OK; ++a) {
-        CTX_HIP(hipMemcpyAsync(ctx->d_stage, host_arrays[a], bytes, hipMemcpyHostToDevice, ctx->stream));
+        NMRFIT_HIP_OR(hipMemcpyAsync(ctx->d_stage, host_arrays[a], bytes, hipMemcpyHostToDevice, ctx->stream),
+                      nmrfit_ctx_destroy(ctx));
         rc = scatter_grid(ctx, ctx->d_stage, dev_arrays[a]);
     }
     if (rc != NMRFIT_OK) {
         nmrfit_ctx_destroy(ctx);
         return rc;
     }
-    CTX_HIP(hipStreamSynchronize(ctx->stream));
-#undef CTX_HIP
+    NMRFIT_HIP_OR(hipStreamSynchronize(ctx->stream), nmrfit_ctx_destroy(ctx));
     *out = ctx;
     return NMRFIT_OK;
 }
@@ -572,21 +579,14 @@ static int generate_one(nmrfit_ctx *ctx, int32_t P, const double *x, int64_t Nou
     const int64_t n_out = 2 * n_contrib + n_fit + n_data;
     if (n_out == 0) return NMRFIT_OK;
     const int64_t D = 4 + 3 * (int64_t)P;
-    double *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = ctx->stream;
-#define CB_HIP(call)                                              \
-    do {                                                          \
-        hipError_t _e = (call);                                   \
-        if (_e != hipSuccess) {                                   \
-            rc = hip_fail(_e, #call, __FILE__, __LINE__);         \
-            goto done;                                            \
-        }                                                         \
-    } while (0)
-    CB_HIP(hipMalloc((void **)&d_in, (size_t)(D + (w_out ? Nout : 0)) * sizeof(double)));
-    CB_HIP(hipMalloc((void **)&d_out, (size_t)n_out * sizeof(double)));
-    CB_HIP(hipMemcpyAsync(d_in, x, (size_t)D * sizeof(double), hipMemcpyHostToDevice, st));
-    if (w_out) CB_HIP(hipMemcpyAsync(d_in + D, w_out, (size_t)Nout * sizeof(double), hipMemcpyHostToDevice, st));
-    {
+    hipStream_t st = ctx->stream;   // (the context's own: synchronised here, never handed to the stream cache)
+    Scratch mem;
+    const auto enqueue_and_wait = [&]() -> int {
+        double *d_in = nullptr, *d_out = nullptr;
+        NMRFIT_HIP(mem.alloc(&d_in, (size_t)(D + (w_out ? Nout : 0))));
+        NMRFIT_HIP(mem.alloc(&d_out, (size_t)n_out));
+        NMRFIT_HIP(hipMemcpyAsync(d_in, x, (size_t)D * sizeof(double), hipMemcpyHostToDevice, st));
+        if (w_out) NMRFIT_HIP(hipMemcpyAsync(d_in + D, w_out, (size_t)Nout * sizeof(double), hipMemcpyHostToDevice, st));
         ResultJob job{};
         job.wc = ctx->d_wc;
         job.w_plain = w_out ? d_in + D : nullptr;   // (centred in the kernel with the context's offset: it works on w - w0)
@@ -602,20 +602,19 @@ static int generate_one(nmrfit_ctx *ctx, int32_t P, const double *x, int64_t Nou
         job.imag = real_out ? d_out + n_contrib : nullptr;
         job.fit = fit_out ? d_out + 2 * n_contrib : nullptr;
         job.data = data_out ? d_out + 2 * n_contrib + n_fit : nullptr;
-        if ((rc = launch_result_one(st, job)) != NMRFIT_OK) goto done;
+        const int launched = launch_result_one(st, job);
+        if (launched != NMRFIT_OK) return launched;
         if (n_contrib) {
-            CB_HIP(hipMemcpyAsync(real_out, job.real, (size_t)n_contrib * sizeof(double), hipMemcpyDeviceToHost, st));
-            CB_HIP(hipMemcpyAsync(imag_out, job.imag, (size_t)n_contrib * sizeof(double), hipMemcpyDeviceToHost, st));
+            NMRFIT_HIP(hipMemcpyAsync(real_out, job.real, (size_t)n_contrib * sizeof(double), hipMemcpyDeviceToHost, st));
+            NMRFIT_HIP(hipMemcpyAsync(imag_out, job.imag, (size_t)n_contrib * sizeof(double), hipMemcpyDeviceToHost, st));
         }
-        if (n_fit) CB_HIP(hipMemcpyAsync(fit_out, job.fit, (size_t)n_fit * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (n_data) CB_HIP(hipMemcpyAsync(data_out, job.data, (size_t)n_data * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    CB_HIP(hipStreamSynchronize(st));
-#undef CB_HIP
-done:
-    if (rc != NMRFIT_OK) (void)hipStreamSynchronize(st);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
+        if (n_fit) NMRFIT_HIP(hipMemcpyAsync(fit_out, job.fit, (size_t)n_fit * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (n_data) NMRFIT_HIP(hipMemcpyAsync(data_out, job.data, (size_t)n_data * sizeof(double), hipMemcpyDeviceToHost, st));
+        NMRFIT_HIP(hipStreamSynchronize(st));
+        return NMRFIT_OK;
+    };
+    rc = enqueue_and_wait();
+    if (rc != NMRFIT_OK) (void)hipStreamSynchronize(st);   // what was enqueued may still use the buffers `mem` frees
     return rc;
 }
 

@@ -66,6 +66,10 @@ struct DeviceInfo {
     char arch[64] = {0};
 };
 int device_info_cached(int device, DeviceInfo *out);      // cabi.hip: compute units and arch name, once per process
+// cabi.hip: the device check of every entry point that takes a device index (a device is visible, the index is in range,
+// it is a gfx950), which also makes it the calling thread's current device
+int use_device(int device, DeviceInfo *info = nullptr);
+int check_spectra_count(const char *who, int32_t S);      // cabi.hip: 1..65535 spectra per call (a launch's grid.y / grid.x)
 hipError_t take_stream(int device, hipStream_t *out);     // cabi.hip: a recycled (or new) non-blocking stream
 void give_stream(int device, hipStream_t s);              // ... handed back idle (synchronised)
 int hip_fail(hipError_t e, const char *what, const char *file, int line);

@@ -11,7 +11,7 @@
 // baselines and the area's sum are compensated sums in a fixed order that depends on the spectrum alone (the host's
 // pinv @ y and np.sum orders cannot be restated): a spectrum's values are bit-identical alone or in any batch.  No
 // atomics, no scratch; every loop is bounded (the baselines stop after 100 passes, NaN spectra included).
-#include "nmrfit_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 
 #include <algorithm>
@@ -435,67 +435,12 @@ __global__ __launch_bounds__(kPickWaves * kWave) void peaks_pick_kernel(const Pe
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
-int check_device(int device)
-{
-    int n = 0;
-    int rc = nmrfit_device_count(&n);
-    if (rc != NMRFIT_OK) return rc;
-    if (n == 0) {
-        set_error("no HIP device visible: libnmrfit_amd has no CPU fallback");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    NMRFIT_HIP(hipSetDevice(device));
-    DeviceInfo prop;
-    if ((rc = device_info_cached(device, &prop)) != NMRFIT_OK) return rc;
-    if (strncmp(prop.arch, "gfx950", 6) != 0) {
-        set_error(std::string("device is ") + prop.arch + ", this library is built for gfx950 only");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    return NMRFIT_OK;
-}
-
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t alloc(T **p, size_t n)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = (T *)q;
-        return e;
-    }
-};
-
-struct StreamLease {
-    int device;
-    hipStream_t s = nullptr;
-    explicit StreamLease(int d) : device(d) {}
-    ~StreamLease()
-    {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            give_stream(device, s);
-        }
-    }
-};
-
 // the batch's layout; order may be NULL (the diagnostic: no slots)
 int plan(const char *who, int32_t S, const int64_t *N, const double *w, const double *u, const double *edges,
          const int64_t *order, const double *thresh, std::vector<PeakSpec> *specs)
 {
-    if (S < 1 || S > 65535) {
-        set_error(std::string(who) + ": S must be 1..65535");
-        return NMRFIT_E_INVALID;
-    }
+    int rc = check_spectra_count(who, S);
+    if (rc != NMRFIT_OK) return rc;
     if (!N || !w || !u || !edges) {
         set_error(std::string(who) + ": null pointer");
         return NMRFIT_E_INVALID;
@@ -546,10 +491,10 @@ int plan(const char *who, int32_t S, const int64_t *N, const double *w, const do
 int run(int device, int32_t S, const std::vector<PeakSpec> &specs, const double *w, const double *u, const double *edges,
         double *U_out, double *S_out, double *baseline, int64_t *count, int64_t *peak_idx, double *peak_val)
 {
-    int rc = check_device(device);
+    int rc = use_device(device);
     if (rc != NMRFIT_OK) return rc;
     StreamLease lease(device);
-    NMRFIT_HIP(take_stream(device, &lease.s));
+    NMRFIT_HIP(lease.take());
     hipStream_t st = lease.s;
     Scratch mem;
     const PeakSpec &last = specs.back();

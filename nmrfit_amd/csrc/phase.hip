@@ -9,7 +9,7 @@
 // in any batch, in the score kernel or inside the optimiser.  No atomics.
 //
 // Every arithmetic step that restates numpy or scipy is written in their operation order with contraction off.
-#include "nmrfit_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 
 #include <algorithm>
@@ -443,35 +443,10 @@ __global__ __launch_bounds__(kPhaseMaxThreads) void phase_nm_kernel(const double
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
-int check_device(int device)
-{
-    int n = 0;
-    int rc = nmrfit_device_count(&n);
-    if (rc != NMRFIT_OK) return rc;
-    if (n == 0) {
-        set_error("no HIP device visible: libnmrfit_amd has no CPU fallback");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    NMRFIT_HIP(hipSetDevice(device));
-    DeviceInfo prop;
-    if ((rc = device_info_cached(device, &prop)) != NMRFIT_OK) return rc;
-    if (strncmp(prop.arch, "gfx950", 6) != 0) {
-        set_error(std::string("device is ") + prop.arch + ", this library is built for gfx950 only");
-        return NMRFIT_E_NO_DEVICE;
-    }
-    return NMRFIT_OK;
-}
-
 int check_spectra(const char *who, int32_t S, const int64_t *N, const double *u, const double *v, std::vector<int64_t> *off)
 {
-    if (S < 1 || S > 65535) {
-        set_error(std::string(who) + ": S must be 1..65535");
-        return NMRFIT_E_INVALID;
-    }
+    int rc = check_spectra_count(who, S);
+    if (rc != NMRFIT_OK) return rc;
     if (!N || !u || !v) {
         set_error(std::string(who) + ": null pointer");
         return NMRFIT_E_INVALID;
@@ -486,37 +461,6 @@ int check_spectra(const char *who, int32_t S, const int64_t *N, const double *u,
     }
     return NMRFIT_OK;
 }
-
-// device buffers of one call, freed on every path
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t alloc(T **p, size_t n)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = (T *)q;
-        return e;
-    }
-};
-
-struct StreamLease {
-    int device;
-    hipStream_t s = nullptr;
-    explicit StreamLease(int d) : device(d) {}
-    ~StreamLease()
-    {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            give_stream(device, s);
-        }
-    }
-};
 
 int upload_spectra(hipStream_t st, Scratch &mem, const std::vector<int64_t> &off, const double *u, const double *v,
                    double **d_u, double **d_v, int64_t **d_off)
@@ -541,10 +485,10 @@ int max_threads(const std::vector<int64_t> &off)
 int run_nm(int device, int kind, int32_t S, const std::vector<int64_t> &off, const double *u, const double *v,
            const double *x0, double *x, double *f, int32_t *nfev, int32_t *nit, int32_t *status)
 {
-    int rc = check_device(device);
+    int rc = use_device(device);
     if (rc != NMRFIT_OK) return rc;
     StreamLease lease(device);
-    NMRFIT_HIP(take_stream(device, &lease.s));
+    NMRFIT_HIP(lease.take());
     hipStream_t st = lease.s;
     Scratch mem;
     double *d_u = nullptr, *d_v = nullptr, *d_x0 = nullptr, *d_x = nullptr, *d_f = nullptr;
@@ -579,10 +523,10 @@ int run_nm(int device, int kind, int32_t S, const std::vector<int64_t> &off, con
 int run_scores(int device, int kind, int32_t S, const std::vector<int64_t> &off, const double *u, const double *v,
                int32_t M, const double *cand, const int64_t *n_mean, double *score, int32_t *empty)
 {
-    int rc = check_device(device);
+    int rc = use_device(device);
     if (rc != NMRFIT_OK) return rc;
     StreamLease lease(device);
-    NMRFIT_HIP(take_stream(device, &lease.s));
+    NMRFIT_HIP(lease.take());
     hipStream_t st = lease.s;
     Scratch mem;
     double *d_u = nullptr, *d_v = nullptr, *d_c = nullptr, *d_s = nullptr;

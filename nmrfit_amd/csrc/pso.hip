@@ -33,7 +33,7 @@
 //       its last-ticket workgroup)                                                -> 2 launches
 //   larger:  the same with the final reduction as its own single-workgroup launch -> 3 launches
 // Multi-rank generations run apply as its own launch after the all-gather.
-#include "nmrfit_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 #include "pso_update.h"
 
@@ -662,15 +662,6 @@ int nmrfit_pso_create(nmrfit_ctx *ctx, int64_t S_local, int64_t S_global, int64_
     if (getenv("NMRFIT_NO_FUSED_TAIL")) pso->fused_tail = false;     // A/B knob
     const size_t sd = (size_t)std::max<int64_t>(S_local * D, 1) * sizeof(double);
     const size_t s1 = (size_t)std::max<int64_t>(S_local, 1) * sizeof(double);
-#define PSO_HIP(call)                                                   \
-    do {                                                                \
-        hipError_t _e = (call);                                         \
-        if (_e != hipSuccess) {                                         \
-            int _rc = hip_fail(_e, #call, __FILE__, __LINE__);          \
-            nmrfit_pso_destroy(pso);                                    \
-            return _rc;                                                 \
-        }                                                               \
-    } while (0)
     // ONE allocation for the whole swarm state (every hipMalloc / hipFree is a synchronising call; a default fit
     // is 30 ms).  Layout: 256-byte aligned pieces; fp[S] right behind p[S x D] (the objective kernel's fused
     // personal-best step finds fp from p without another pointer argument, objective.hip).
@@ -679,47 +670,47 @@ int nmrfit_pso_create(nmrfit_ctx *ctx, int64_t S_local, int64_t S_global, int64_
         // (fg, best_f, g[D], best_x[D] | generations, stop code): two copies, 256-byte aligned, the flags right behind
         // the doubles -- the deferred fold of a fused launch reads one and writes the other (PsoFused::flip)
         const size_t state_bytes = (((size_t)(2 + 2 * D) * sizeof(double) + 2 * sizeof(long long)) + 255) & ~(size_t)255;
-        const size_t sizes[] = {(size_t)D * sizeof(double), (size_t)D * sizeof(double), sd, sd, sd, sd,
-                                (size_t)std::max<int64_t>(S_local * D, 0) * sizeof(double) + s1, s1,
-                                (size_t)(D + 1) * sizeof(double), 2 * state_bytes,
-                                (size_t)std::max<int64_t>(S_local * D, 0) * sizeof(double) + s1,
-                                nposts * sizeof(double), nposts * sizeof(long long), 256};
-        size_t off[sizeof(sizes) / sizeof(sizes[0])], total = 0;
-        for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-            off[i] = total;
-            total += (sizes[i] + 255) & ~(size_t)255;
-        }
-        PSO_HIP(hipMalloc(&pso->d_block, total));
+        const size_t p_bytes = (size_t)std::max<int64_t>(S_local * D, 0) * sizeof(double) + s1;   // p[S x D], fp[S]
+        Carver c;
+        const size_t o_lb = c.take((size_t)D * sizeof(double)), o_ub = c.take((size_t)D * sizeof(double));
+        const size_t o_x = c.take(sd), o_v = c.take(sd), o_x2 = c.take(sd), o_v2 = c.take(sd);
+        const size_t o_p = c.take(p_bytes), o_fx = c.take(s1), o_cand = c.take((size_t)(D + 1) * sizeof(double));
+        const size_t o_best = c.take(2 * state_bytes), o_p_alt = c.take(p_bytes);
+        const size_t o_part_val = c.take(nposts * sizeof(double)), o_part_idx = c.take(nposts * sizeof(long long));
+        const size_t o_ticket = c.take(256);
+        NMRFIT_HIP_OR(hipMalloc(&pso->d_block, c.total), nmrfit_pso_destroy(pso));
         unsigned char *base = reinterpret_cast<unsigned char *>(pso->d_block);
-        pso->d_lb = reinterpret_cast<double *>(base + off[0]);
-        pso->d_ub = reinterpret_cast<double *>(base + off[1]);
-        pso->d_x = reinterpret_cast<double *>(base + off[2]);
-        pso->d_v = reinterpret_cast<double *>(base + off[3]);
-        pso->d_x2 = reinterpret_cast<double *>(base + off[4]);
-        pso->d_v2 = reinterpret_cast<double *>(base + off[5]);
-        pso->d_p = reinterpret_cast<double *>(base + off[6]);
+        pso->d_lb = reinterpret_cast<double *>(base + o_lb);
+        pso->d_ub = reinterpret_cast<double *>(base + o_ub);
+        pso->d_x = reinterpret_cast<double *>(base + o_x);
+        pso->d_v = reinterpret_cast<double *>(base + o_v);
+        pso->d_x2 = reinterpret_cast<double *>(base + o_x2);
+        pso->d_v2 = reinterpret_cast<double *>(base + o_v2);
+        pso->d_p = reinterpret_cast<double *>(base + o_p);
         pso->d_fp = pso->d_p + S_local * D;
-        pso->d_fx = reinterpret_cast<double *>(base + off[7]);
-        pso->d_cand_own = reinterpret_cast<double *>(base + off[8]);
+        pso->d_fx = reinterpret_cast<double *>(base + o_fx);
+        pso->d_cand_own = reinterpret_cast<double *>(base + o_cand);
         pso->d_cand = pso->d_cand_own;
-        pso->d_best = reinterpret_cast<double *>(base + off[9]);
+        pso->d_best = reinterpret_cast<double *>(base + o_best);
         pso->d_flags = reinterpret_cast<long long *>(pso->d_best + 2 + 2 * D);
-        pso->d_p_alt = reinterpret_cast<double *>(base + off[10]);
-        pso->d_best_alt = reinterpret_cast<double *>(base + off[9] + state_bytes);
+        pso->d_p_alt = reinterpret_cast<double *>(base + o_p_alt);
+        pso->d_best_alt = reinterpret_cast<double *>(base + o_best + state_bytes);
         pso->d_flags_alt = reinterpret_cast<long long *>(pso->d_best_alt + 2 + 2 * D);
-        PSO_HIP(hipMemsetAsync(pso->d_best, 0, 2 * state_bytes, ctx->stream));
-        pso->d_part_val = reinterpret_cast<double *>(base + off[11]);
-        pso->d_part_idx = reinterpret_cast<long long *>(base + off[12]);
-        pso->d_ticket = reinterpret_cast<unsigned *>(base + off[13]);
+        NMRFIT_HIP_OR(hipMemsetAsync(pso->d_best, 0, 2 * state_bytes, ctx->stream), nmrfit_pso_destroy(pso));
+        pso->d_part_val = reinterpret_cast<double *>(base + o_part_val);
+        pso->d_part_idx = reinterpret_cast<long long *>(base + o_part_idx);
+        pso->d_ticket = reinterpret_cast<unsigned *>(base + o_ticket);
         // (posts beyond the workgroups a swarm of this size launches are never read)
         const size_t used_posts = (size_t)std::min<int64_t>((S_local + kSelectWaves - 1) / kSelectWaves + 1, kSelectMaxPosts);
-        PSO_HIP(hipMemsetAsync(pso->d_part_idx, 0, used_posts * sizeof(long long), ctx->stream));
-        PSO_HIP(hipMemsetAsync(pso->d_ticket, 0, sizeof(unsigned), ctx->stream));
+        NMRFIT_HIP_OR(hipMemsetAsync(pso->d_part_idx, 0, used_posts * sizeof(long long), ctx->stream),
+                      nmrfit_pso_destroy(pso));
+        NMRFIT_HIP_OR(hipMemsetAsync(pso->d_ticket, 0, sizeof(unsigned), ctx->stream), nmrfit_pso_destroy(pso));
     }
-    PSO_HIP(hipMemcpyAsync(pso->d_lb, lower, (size_t)D * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PSO_HIP(hipMemcpyAsync(pso->d_ub, upper, (size_t)D * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PSO_HIP(hipStreamSynchronize(ctx->stream));
-#undef PSO_HIP
+    NMRFIT_HIP_OR(hipMemcpyAsync(pso->d_lb, lower, (size_t)D * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+                  nmrfit_pso_destroy(pso));
+    NMRFIT_HIP_OR(hipMemcpyAsync(pso->d_ub, upper, (size_t)D * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+                  nmrfit_pso_destroy(pso));
+    NMRFIT_HIP_OR(hipStreamSynchronize(ctx->stream), nmrfit_pso_destroy(pso));
     *out = pso;
     return NMRFIT_OK;
 }

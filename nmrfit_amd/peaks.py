@@ -21,6 +21,8 @@ import scipy.interpolate
 import scipy.ndimage
 import scipy.signal
 
+from ._cabi import _MAX_SPECTRA_PER_CALL
+
 
 class Peak:
     """One line of a spectrum: loc, height, bounds = loc -+ 2 FWHM, width (FWHM), area."""
@@ -187,7 +189,6 @@ def sample_noise(X, Y, xstart, xstop):
 
 UPSAMPLE = 100                     # AutoPeakSelector: np.linspace(w.min(), w.max(), len(w) * 100)
 POINT_BUDGET = 1 << 26             # upsampled points per library call: U and S take 16 bytes each point (1 GiB)
-_MAX_SPECTRA_PER_CALL = 65535      # the library's limit per call
 
 
 def grid_points(wmin, wmax, M, k):

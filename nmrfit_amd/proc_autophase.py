@@ -12,6 +12,8 @@ Units follow the reference: ``ps2`` takes radians, ``ps`` and the scores take DE
 import numpy as np
 import scipy.optimize
 
+from ._cabi import _MAX_SPECTRA_PER_CALL
+
 
 def _ramp(size, p0, p1):
     """exp(i (p0 + p1 j / size)), j the array index: the order of operations of the reference."""
@@ -109,9 +111,6 @@ def _pack(spectra):
     v = np.ascontiguousarray(np.concatenate([z.imag if np.iscomplexobj(z) else np.zeros(z.shape) for z in zs]),
                              dtype=np.float64)
     return N, u, v
-
-
-_MAX_SPECTRA_PER_CALL = 65535     # the library's limit per call (a launch's grid.y / grid.x): larger lists are cut
 
 
 def _chunks(N):

@@ -145,6 +145,60 @@ def test_batch_argument_validation_needs_no_gpu():
         assert ei.value.code == _cabi.E_NO_DEVICE
 
 
+def test_every_device_entry_point_reports_a_bad_device_index_alike():
+    """The eight entry points that take a device index share one device check: with arguments that are otherwise valid and
+    an index no machine has, each returns NMRFIT_E_NO_DEVICE with the same message -- that no device is visible (or, on
+    a box without a driver, what nmrfit_device_count says there) where there is no GPU, that the index is out of range
+    where there is one."""
+    L = _cabi.lib()
+    dev, S, n, M, P, swarm = 1 << 20, 2, 16, 1, 1, 8
+    D = 4 + 3 * P
+    w = np.tile(np.linspace(0.0, 1.0, n), S)
+    u, v, wt = np.cos(7.0 * w), np.sin(7.0 * w), np.ones(S * n)
+    N = np.full(S, n, dtype=np.int64)
+    peaks = np.full(S, P, dtype=np.int32)
+    lower, upper = np.zeros(S * D), np.ones(S * D)
+    params = (_cabi.PsoParams * S)(*[_cabi.PsoParams(0.5, 0.5, 0.5, 1e-8, 1e-8, k + 1) for k in range(S)])
+    cand, x0 = np.zeros(2 * S * M), np.zeros(2 * S)
+    score, x, f = np.zeros(S * M), np.zeros(2 * S), np.zeros(S)
+    status, nfev, nit = (np.zeros(S, dtype=np.int32) for _ in range(3))
+    n_mean, order = np.full(S, 4, dtype=np.int64), np.ones(S, dtype=np.int64)
+    edges, thresh, baseline = np.zeros(10 * S), np.zeros(S), np.zeros(S)
+    count = np.zeros(S, dtype=np.int64)
+    nslots = S * ((100 * n - 1) // 2 + 1)
+    pidx, pval = np.zeros(3 * nslots, dtype=np.int64), np.zeros(5 * nslots)
+    U, Sm = np.zeros(100 * S * n), np.zeros(100 * S * n)
+    out = ctypes.c_void_p()
+    p = _cabi.ptr
+    calls = {
+        "nmrfit_ctx_create": lambda: L.nmrfit_ctx_create(dev, n, p(w), p(u), p(v), p(wt), ctypes.byref(out)),
+        "nmrfit_batch_create": lambda: L.nmrfit_batch_create(dev, S, n, p(w), p(u), p(v), p(wt), p(peaks), p(lower), p(upper),
+                                                             swarm, params, 0, 0, ctypes.byref(out)),
+        "nmrfit_phase_scores": lambda: L.nmrfit_phase_scores(dev, _cabi.PHASE_ACME, S, p(N), p(u), p(v), M, p(cand), p(score),
+                                                             p(status)),
+        "nmrfit_phase_brute_levels": lambda: L.nmrfit_phase_brute_levels(dev, S, p(N), p(n_mean), p(u), p(v), M, p(cand),
+                                                                         p(score)),
+        "nmrfit_phase_estimate": lambda: L.nmrfit_phase_estimate(dev, _cabi.PHASE_ACME, S, p(N), p(u), p(v), p(x0), p(x), p(f),
+                                                                 p(nfev), p(nit), p(status)),
+        "nmrfit_diag_phase_nm_rosenbrock": lambda: L.nmrfit_diag_phase_nm_rosenbrock(dev, S, p(x0), p(x), p(f), p(nfev), p(nit)),
+        "nmrfit_peaks_pick": lambda: L.nmrfit_peaks_pick(dev, S, p(N), p(w), p(u), p(edges), p(order), p(thresh), p(baseline),
+                                                         p(count), p(pidx), p(pval)),
+        "nmrfit_diag_peaks_smooth": lambda: L.nmrfit_diag_peaks_smooth(dev, S, p(N), p(w), p(u), p(edges), p(U), p(Sm)),
+    }
+    visible = ctypes.c_int(0)
+    if L.nmrfit_device_count(ctypes.byref(visible)) != _cabi.OK:   # (no driver at all: the runtime's own refusal is passed on)
+        expected = L.nmrfit_last_error()
+        assert expected.startswith(b"hipGetDeviceCount failed: ")
+    elif visible.value == 0:
+        expected = b"no HIP device visible: libnmrfit_amd has no CPU fallback"
+    else:
+        expected = b"device index out of range"
+    for name, call in calls.items():
+        assert call() == _cabi.E_NO_DEVICE, name
+        assert L.nmrfit_last_error() == expected, (name, L.nmrfit_last_error())
+    assert not out.value
+
+
 def test_variant_names():
     import pytest
     assert _cabi.variant_id("farfield") == _cabi.VARIANT_FARFIELD == 6
