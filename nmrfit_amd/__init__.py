@@ -11,12 +11,15 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.Data(w, u, v)                                     (nmrfit/containers.py:8, scripted use)
     nmrfit_amd.shift_phase_many(datas, method='auto')            Data.shift_phase for many spectra: the phase search on the DEVICE
     nmrfit_amd.select_peaks_many(datas, method='auto')           Data.select_peaks for many spectra: peak picking on the DEVICE
+    nmrfit_amd.utils.compute_weights_many(ws, peaks_list)        FitUtility._compute_weights for many spectra on the DEVICE
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
 asked for by shift_phase_many / proc_autophase.approximate_phase_many and select_peaks_many / peaks.find_peaks_many
-(opt-in: Data.shift_phase and Data.select_peaks stay the reference's host paths).  The other once-per-dataset helpers
-(bounds, weights) are host code as in the reference.  Instrument I/O (nmrfit.load), the
+(opt-in: Data.shift_phase and Data.select_peaks stay the reference's host paths).  The error weights of a fit are host
+code as in the reference unless fit_many(jobs, device_weights=True) / FitBatch(regions=...) /
+utils.compute_weights_many ask for them on the device (include/nmrfit_amd_prep.h; bit-identical to the host's); the
+bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401

@@ -151,6 +151,14 @@ _DIAG_NAMES = (
     "nmrfit_diag_peaks_smooth")
 DIAG_SIGNATURES = {k: ALL_SIGNATURES[k] for k in _DIAG_NAMES}
 SIGNATURES = {k: v for k, v in ALL_SIGNATURES.items() if k not in DIAG_SIGNATURES}
+# PREP_SIGNATURES: include/nmrfit_amd_prep.h (preparation stages of batched fits on the device: a table of its own, the
+# product header stays as thin as it is)
+PREP_SIGNATURES = {
+    "nmrfit_weights_build": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_create_regions": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _INT, _INT,
+                                    _c_void_pp],
+}
+WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
 _LIB = None
 
@@ -252,7 +260,7 @@ def lib():
         # HIP call this library makes.  A value the user exported wins.
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
-        for name, argtypes in ALL_SIGNATURES.items():
+        for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

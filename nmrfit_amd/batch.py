@@ -13,7 +13,7 @@ import ctypes
 
 import numpy as np
 
-from . import _cabi, equations, pso
+from . import _cabi, equations, pso, utils
 
 
 class FitBatch:
@@ -27,12 +27,16 @@ class FitBatch:
     omega, phip, phig, minstep, minfunc : scalars or length-K sequences
     variant : "default" or "farfield" (what ``fit`` would select for these shapes)
     fit_im : False, True (the reference's imaginary term) or "sum" (every peak; "default" kernel), for the whole batch
+    regions : None, or K entries ``(edges, level)`` (``utils.weight_regions``; None: unit weights) -- the weights of the
+              WHOLE batch are then built on the device (nmrfit_batch_create_regions, csrc/weights.hip: bit for bit what
+              ``utils.compute_weights`` gives) and the ``spectra`` tuples are ``(w, u, v)`` (a fourth element of None is
+              allowed)
     """
 
     def __init__(self, spectra, lowers, uppers, swarmsize=pso.DEFAULTS["swarmsize"], seeds=None,
                  omega=pso.DEFAULTS["omega"], phip=pso.DEFAULTS["phip"], phig=pso.DEFAULTS["phig"],
                  minstep=pso.DEFAULTS["minstep"], minfunc=pso.DEFAULTS["minfunc"], variant="default", fit_im=False,
-                 device=0):
+                 device=0, regions=None):
         self._lib = _cabi.lib()
         self._h = ctypes.c_void_p()
         K = len(spectra)
@@ -40,9 +44,21 @@ class FitBatch:
             raise ValueError("FitBatch: as many boxes as spectra, at least one")
         Ns = np.array([len(sp[0]) for sp in spectra], dtype=np.int64)
         noff = np.concatenate(([0], np.cumsum(Ns)))
-        planes = [np.empty(int(noff[-1])) for _ in range(4)]
+        if regions is not None:
+            if len(regions) != K:
+                raise ValueError("FitBatch: one entry of regions per spectrum")
+            for k, sp in enumerate(spectra):
+                if len(sp) not in (3, 4) or (len(sp) == 4 and sp[3] is not None):
+                    raise ValueError("FitBatch: with regions a spectrum is (w, u, v): the batch builds every fit's "
+                                     "weights or none (fit %d)" % k)
+            spectra = [tuple(sp[:3]) for sp in spectra]
+            R, edges, level = utils.pack_regions(regions)
+        planes = [np.empty(int(noff[-1])) for _ in range(4 if regions is None else 3)]
         for k, sp in enumerate(spectra):
-            if len(sp) != 4 or any(len(a) != Ns[k] for a in sp) or Ns[k] == 0:
+            if regions is not None:
+                if any(len(a) != Ns[k] for a in sp) or Ns[k] == 0:
+                    raise ValueError("FitBatch: w, u, v of a spectrum have the same non-zero length (fit %d)" % k)
+            elif len(sp) != 4 or any(len(a) != Ns[k] for a in sp) or Ns[k] == 0:
                 raise ValueError("FitBatch: w, u, v, weights of a spectrum have the same non-zero length (fit %d)" % k)
             for a, plane in zip(sp, planes):
                 plane[noff[k]:noff[k + 1]] = a      # (contiguous float64: the reference hands out reversed views, core.py:60)
@@ -78,6 +94,14 @@ class FitBatch:
         prm = (_cabi.PsoParams * K)()
         for k in range(K):
             prm[k] = _cabi.PsoParams(om[k], pp[k], pg[k], ms[k], mf[k], self.seeds[k])
+        if regions is not None:
+            _cabi.check(self._lib.nmrfit_batch_create_regions(int(device), K, _cabi.ptr(Ns), _cabi.ptr(planes[0]),
+                                                              _cabi.ptr(planes[1]), _cabi.ptr(planes[2]), _cabi.ptr(R),
+                                                              _cabi.ptr(edges), _cabi.ptr(level), _cabi.ptr(self.P),
+                                                              _cabi.ptr(lower), _cabi.ptr(upper), _cabi.ptr(self.Ss), prm,
+                                                              _cabi.variant_id(variant), equations.fit_im_mode(fit_im),
+                                                              ctypes.byref(self._h)))
+            return
         _cabi.check(self._lib.nmrfit_batch_create_ragged(int(device), K, _cabi.ptr(Ns), _cabi.ptr(planes[0]),
                                                          _cabi.ptr(planes[1]), _cabi.ptr(planes[2]), _cabi.ptr(planes[3]),
                                                          _cabi.ptr(self.P), _cabi.ptr(lower), _cabi.ptr(upper), _cabi.ptr(self.Ss), prm,

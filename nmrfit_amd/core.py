@@ -31,7 +31,8 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
     return f
 
 
-def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, **kwargs):
+def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
+             **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -69,7 +70,11 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       ``nmrfit_amd.rendezvous.Channel`` to gather over (a caller that already has one); else one is made.
     * ``devices=[0, 1, ...]`` (or ``"all"``): the same replicas WITHOUT a launcher -- this one process drives several
       GPUs, a host thread per device, job k on ``devices[k % len(devices)]``; each device runs its share as device
-      batches of its own.  Nothing crosses devices.  (``shard`` and ``devices`` exclude each other.)"""
+      batches of its own.  Nothing crosses devices.  (``shard`` and ``devices`` exclude each other.)
+    * ``device_weights=True``: the error weights of the fits of a device batch (``utils.compute_weights``, the one
+      O(N x P) stage the preparation thread otherwise runs per fit) are built on the GPU as part of the batch's creation
+      (csrc/weights.hip; ``FitBatch(regions=...)``), bit for bit the host's, so ``params`` and ``error`` do not change.
+      ``f.weights`` of such a fit is made by the host routine on first access.  Fits that run alone take the host path."""
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     if devices is not None:
@@ -83,13 +88,19 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
         devices = [int(d) for d in devices]
         if not devices:
             raise ValueError("fit_many: no devices")
-        return _fit_many_devices(jobs, threads, batch, kwargs, devices, generate)
+        return _fit_many_devices(jobs, threads, batch, kwargs, devices, generate, device_weights)
     if shard:
         from . import rendezvous
         rank, _, world = rendezvous.env_rank_world()
         if world > 1:
-            return _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=channel, generate=generate)
-    return _fit_many_local(jobs, threads, batch, kwargs, generate)
+            return _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=channel, generate=generate,
+                                     device_weights=device_weights)
+    return _fit_many_local(jobs, threads, batch, kwargs, generate, **_flags(device_weights))
+
+
+def _flags(device_weights):
+    """The opt-in arguments of _fit_many_local, passed on only when they are set."""
+    return {"device_weights": True} if device_weights else {}
 
 
 def _result_record(f):
@@ -109,7 +120,8 @@ def _with_device(job, shared_options, device, force=False):
     return dict(job, options=opts)
 
 
-def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, local=None, generate=False):
+def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, local=None, generate=False,
+                      device_weights=False):
     """Jobs r, r + world, ... on this rank's GPU; every rank returns every result (the other ranks' as FitUtility
     objects holding ``params`` / ``error`` / ``seed``; their ``weights`` are recomputed on demand only by ``fit``)."""
     import json
@@ -122,7 +134,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
             sys.stderr.write("nmrfit: %s\n" % note)
 
         def local(my_jobs):
-            return _fit_many_local(my_jobs, threads, batch, kwargs, generate)
+            return _fit_many_local(my_jobs, threads, batch, kwargs, generate, **_flags(device_weights))
     else:
         device = None
     # the ranks meet BEFORE they fit: a mis-launched world shows at once, and the channel's connect deadline does not
@@ -153,7 +165,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
     return out
 
 
-def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False):
+def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, device_weights=False):
     """Job k on devices[k % len(devices)], one host thread per device (the library releases the GIL inside its calls;
     every call binds its own device), results back in job order."""
     from concurrent.futures import ThreadPoolExecutor
@@ -162,7 +174,7 @@ def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False):
 
     def one(i):
         mine = [_with_device(jobs[k], shared, devices[i], force=True) for k in shares[i]]
-        return _fit_many_local(mine, threads, batch, kwargs, generate)
+        return _fit_many_local(mine, threads, batch, kwargs, generate, **_flags(device_weights))
     out = [None] * len(jobs)
     with ThreadPoolExecutor(max_workers=len(devices)) as pool:
         for idx, res in zip(shares, pool.map(one, range(len(devices)))):
@@ -202,7 +214,7 @@ def _batch_jobs(n):
     return min(BATCH_JOBS_MAX, max(BATCH_JOBS_MIN, -(-n // PIPELINE_BATCHES)))
 
 
-def _fit_many_local(jobs, threads, batch, kwargs, generate=False):
+def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights=False):
     from concurrent.futures import ThreadPoolExecutor
     from ._cabi import NmrfitError
     scale = 1 if generate is True else generate      # (False: no reconstruction)
@@ -237,7 +249,7 @@ def _fit_many_local(jobs, threads, batch, kwargs, generate=False):
 
         def prepare(span):
             for i in span:
-                plans[i] = fits[i]._plan()
+                plans[i] = fits[i]._plan(device_weights=bool(device_weights))
             return group([(i, fits[i]._batch_key(plans[i])) for i in span])
 
         leftover = []
@@ -337,10 +349,15 @@ def _batch_create(fits, plans, key):
     from .batch import FitBatch
     device, _, _, variant, _, _, fit_im = key
     swarmsize = [int(p['swarmsize']) for p in plans]
-    spectra = [(f.data.w, f.data.u, f.data.v, f.weights) for f in fits]
+    # (all or nothing: the plans of one fit_many call either all carry their regions -- device_weights -- or none does)
+    regions = [p['regions'] for p in plans] if all('regions' in p for p in plans) else None
+    if regions is None:
+        spectra = [(f.data.w, f.data.u, f.data.v, f.weights) for f in fits]
+    else:
+        spectra = [(f.data.w, f.data.u, f.data.v) for f in fits]
     kw = {name: [p['kw'][name] for p in plans] for name in ("omega", "phip", "phig", "minstep", "minfunc")}
     fb = FitBatch(spectra, [f.lower for f in fits], [f.upper for f in fits], swarmsize=swarmsize,
-                  seeds=[p['seed'] for p in plans], variant=variant, fit_im=fit_im, device=device, **kw)
+                  seeds=[p['seed'] for p in plans], variant=variant, fit_im=fit_im, device=device, regions=regions, **kw)
     return fb, fits, plans, key
 
 

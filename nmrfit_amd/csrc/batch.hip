@@ -18,7 +18,9 @@
 #include "batch_internal.h"
 #include "host_call.h"
 #include "nmrfit_amd_diag.h"
+#include "nmrfit_amd_prep.h"
 #include "result_internal.h"
+#include "weights_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -327,17 +329,20 @@ struct FitMem {
 
 static int part_destroy(BatchPart *b);
 
-// (w, u, v, weights: the part's fits one after the other, fit k's Nk[k] points at offset sum_{i<k} Nk[i])
+// (w, u, v, weights: the part's fits one after the other, fit k's Nk[k] points at offset sum_{i<k} Nk[i].  `weights`
+// null: the weights plane is built on the device from the part's regions -- R[k] of them per fit, their bounds and
+// levels concatenated in edges and level, already checked (check_weight_regions) -- by the two launches of weights.hip)
 static int part_create(int device, int32_t K, const int64_t *Nk, const double *w, const double *u, const double *v,
-                       const double *weights, const int32_t *P, const double *lower, const double *upper,
-                       const int64_t *swarm, const nmrfit_pso_params *params, int variant, int fit_im, BatchPart **out)
+                       const double *weights, const int32_t *R, const double *edges, const double *level, const int32_t *P,
+                       const double *lower, const double *upper, const int64_t *swarm, const nmrfit_pso_params *params,
+                       int variant, int fit_im, BatchPart **out)
 {
     if (!out) {
         set_error("null out pointer");
         return NMRFIT_E_INVALID;
     }
     *out = nullptr;
-    if (K <= 0 || !Nk || !swarm || !w || !u || !v || !weights || !P || !lower || !upper || !params) {
+    if (K <= 0 || !Nk || !swarm || !w || !u || !v || (!weights && !R) || !P || !lower || !upper || !params) {
         set_error("nmrfit_batch_create: K, N, swarmsize must be > 0 and every array non-null");
         return NMRFIT_E_INVALID;
     }
@@ -448,6 +453,14 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
     const size_t o_bestx = c.take((size_t)b->Dsum * sizeof(double) + (size_t)K * sizeof(int64_t));
     const size_t o_tables = c.take((size_t)9 * (size_t)K * sizeof(BatchFit));
     const size_t o_raw = c.take((size_t)4 * (size_t)Nsum * sizeof(double));
+    // the region tables of a weights plane built here (weights.hip): layout, bounds, levels, the index pairs
+    std::vector<WeightSpec> wspecs;
+    std::vector<int32_t> region_spec;
+    if (!weights) weights_layout(K, Nk, R, &wspecs, &region_spec);
+    const size_t n_regions = region_spec.size();
+    const size_t o_wspecs = c.take(wspecs.size() * sizeof(WeightSpec)), o_rspec = c.take(n_regions * sizeof(int32_t));
+    const size_t o_edges = c.take(2 * n_regions * sizeof(double)), o_level = c.take(n_regions * sizeof(double));
+    const size_t o_pairs = c.take(2 * n_regions * sizeof(int64_t));
     NMRFIT_HIP_OR(hipMalloc(&b->d_block, c.total), part_destroy(b));
     unsigned char *base = reinterpret_cast<unsigned char *>(b->d_block);
     // padding of the grid arrays (weight 0), state blocks
@@ -562,13 +575,34 @@ static int part_create(int device, int32_t K, const int64_t *Nk, const double *w
                   part_destroy(b));
     NMRFIT_HIP_OR(hipMemcpyAsync(b->d_bestx + b->Dsum, b->boff.data(), (size_t)K * sizeof(int64_t), hipMemcpyHostToDevice, b->stream),
                   part_destroy(b));
-    // ---- spectra: four uploads, one scatter kernel, one chunk-table kernel
+    // ---- spectra: four uploads (or three, and the weights plane built from the regions: two launches), one scatter
+    // kernel, one chunk-table kernel
     const size_t plane = (size_t)Nsum * sizeof(double);
     const double *host_arrays[] = {w, u, v, weights};
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < (weights ? 4 : 3); ++a)
         NMRFIT_HIP_OR(hipMemcpyAsync(reinterpret_cast<unsigned char *>(d_raw) + (size_t)a * plane, host_arrays[a], plane,
                                      hipMemcpyHostToDevice, b->stream),
                       part_destroy(b));
+    if (!weights) {
+        NMRFIT_HIP_OR(hipMemcpyAsync(base + o_wspecs, wspecs.data(), wspecs.size() * sizeof(WeightSpec), hipMemcpyHostToDevice, b->stream),
+                      part_destroy(b));
+        if (n_regions) {
+            NMRFIT_HIP_OR(hipMemcpyAsync(base + o_rspec, region_spec.data(), n_regions * sizeof(int32_t), hipMemcpyHostToDevice, b->stream),
+                          part_destroy(b));
+            NMRFIT_HIP_OR(hipMemcpyAsync(base + o_edges, edges, 2 * n_regions * sizeof(double), hipMemcpyHostToDevice, b->stream),
+                          part_destroy(b));
+            NMRFIT_HIP_OR(hipMemcpyAsync(base + o_level, level, n_regions * sizeof(double), hipMemcpyHostToDevice, b->stream),
+                          part_destroy(b));
+        }
+        rc = launch_weights(b->stream, K, reinterpret_cast<const WeightSpec *>(base + o_wspecs),
+                            reinterpret_cast<const int32_t *>(base + o_rspec), (int64_t)n_regions, b->Nmax, d_raw,
+                            reinterpret_cast<const double *>(base + o_edges), reinterpret_cast<const double *>(base + o_level),
+                            reinterpret_cast<int64_t *>(base + o_pairs), d_raw + 3 * (size_t)Nsum);
+        if (rc != NMRFIT_OK) {
+            part_destroy(b);
+            return rc;
+        }
+    }
     NMRFIT_HIP_OR(hipMemcpyAsync(base + o_lball, lower, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream),
                   part_destroy(b));
     NMRFIT_HIP_OR(hipMemcpyAsync(base + o_uball, upper, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, b->stream),
@@ -892,19 +926,18 @@ static int part_of(const nmrfit_batch *b, int32_t k)
 
 }  // namespace
 
-#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
-extern "C" {
-
-int nmrfit_batch_create_ragged(int device, int32_t K, const int64_t *N, const double *w, const double *u, const double *v,
-                               const double *weights, const int32_t *P, const double *lower, const double *upper,
-                               const int64_t *swarmsize, const nmrfit_pso_params *params, int variant, int fit_im, nmrfit_batch **out)
+// nmrfit_batch_create_ragged (weights given) and nmrfit_batch_create_regions (weights null; R, edges, level: checked)
+static int batch_create(int device, int32_t K, const int64_t *N, const double *w, const double *u, const double *v,
+                        const double *weights, const int32_t *R, const double *edges, const double *level, const int32_t *P,
+                        const double *lower, const double *upper, const int64_t *swarmsize, const nmrfit_pso_params *params,
+                        int variant, int fit_im, nmrfit_batch **out)
 {
     if (!out) {
         set_error("null out pointer");
         return NMRFIT_E_INVALID;
     }
     *out = nullptr;
-    if (K <= 0 || !N || !swarmsize || !w || !u || !v || !weights || !P || !lower || !upper || !params) {
+    if (K <= 0 || !N || !swarmsize || !w || !u || !v || (!weights && !R) || !P || !lower || !upper || !params) {
         set_error("nmrfit_batch_create: K, N, swarmsize must be > 0 and every array non-null");
         return NMRFIT_E_INVALID;
     }
@@ -927,11 +960,13 @@ int nmrfit_batch_create_ragged(int device, int32_t K, const int64_t *N, const do
     int nparts = (K >= 6) ? 2 : 1;
     if (const char *e = getenv("NMRFIT_BATCH_STREAMS")) nparts = std::max(1, std::min(atoi(e), (int)std::min<int32_t>(K, 8)));
     for (int p = 0; p <= nparts; ++p) b->first.push_back((int32_t)((int64_t)K * p / nparts));
+    int64_t r0 = 0;   // regions before the part (the region tables are offset per part, as the planes are)
     for (int p = 0; p < nparts; ++p) {
         const int32_t f0 = b->first[(size_t)p], f1 = b->first[(size_t)p + 1];
         const int64_t n0 = b->noff[(size_t)f0];
         BatchPart *part = nullptr;
-        const int rc = part_create(device, f1 - f0, N + f0, w + n0, u + n0, v + n0, weights + n0, P + f0,
+        const int rc = part_create(device, f1 - f0, N + f0, w + n0, u + n0, v + n0, weights ? weights + n0 : nullptr,
+                                   R ? R + f0 : nullptr, edges ? edges + 2 * r0 : nullptr, level ? level + r0 : nullptr, P + f0,
                                    lower + b->boff[(size_t)f0], upper + b->boff[(size_t)f0], swarmsize + f0, params + f0, variant,
                                    fit_im, &part);
         if (rc != NMRFIT_OK) {
@@ -939,9 +974,47 @@ int nmrfit_batch_create_ragged(int device, int32_t K, const int64_t *N, const do
             return rc;
         }
         b->parts.push_back(part);
+        for (int32_t k = f0; R && k < f1; ++k) r0 += R[k];
     }
     *out = b;
     return NMRFIT_OK;
+}
+
+#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
+extern "C" {
+
+int nmrfit_batch_create_ragged(int device, int32_t K, const int64_t *N, const double *w, const double *u, const double *v,
+                               const double *weights, const int32_t *P, const double *lower, const double *upper,
+                               const int64_t *swarmsize, const nmrfit_pso_params *params, int variant, int fit_im, nmrfit_batch **out)
+{
+    if (out && !weights) {   // (reported as batch_create reports the other null arrays)
+        *out = nullptr;
+        set_error("nmrfit_batch_create: K, N, swarmsize must be > 0 and every array non-null");
+        return NMRFIT_E_INVALID;
+    }
+    return batch_create(device, K, N, w, u, v, weights, nullptr, nullptr, nullptr, P, lower, upper, swarmsize, params, variant,
+                        fit_im, out);
+}
+
+int nmrfit_batch_create_regions(int device, int32_t K, const int64_t *N, const double *w, const double *u, const double *v,
+                                const int32_t *R, const double *edges, const double *level, const int32_t *P,
+                                const double *lower, const double *upper, const int64_t *swarmsize,
+                                const nmrfit_pso_params *params, int variant, int fit_im, nmrfit_batch **out)
+{
+    const char *who = "nmrfit_batch_create_regions";
+    if (!out) {
+        set_error("null out pointer");
+        return NMRFIT_E_INVALID;
+    }
+    *out = nullptr;
+    if (!w || !u || !v || !P || !lower || !upper || !swarmsize || !params) {
+        set_error(std::string(who) + ": null pointer");
+        return NMRFIT_E_INVALID;
+    }
+    int64_t n_points = 0, n_regions = 0;
+    const int rc = check_weight_regions(who, K, N, R, edges, level, &n_points, &n_regions);
+    if (rc != NMRFIT_OK) return rc;
+    return batch_create(device, K, N, w, u, v, nullptr, R, edges, level, P, lower, upper, swarmsize, params, variant, fit_im, out);
 }
 
 int nmrfit_batch_create(int device, int32_t K, int64_t N, const double *w, const double *u, const double *v,

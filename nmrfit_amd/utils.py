@@ -59,6 +59,92 @@ def compute_weights(w, peaks, expon=0.5):
     return equations.laplace1d(weights)
 
 
+# grid points a workgroup of the device's fill-and-smooth kernel owns (NMRFIT_WEIGHTS_TILE, include/nmrfit_amd_prep.h)
+WEIGHTS_TILE = 1024
+
+
+def weight_regions(w, peaks, expon=0.5):
+    """The host half of ``compute_weights``, for the device form (``compute_weights_many``, ``FitBatch(regions=...)``):
+    ``(edges[R, 2], level[R])`` -- every peak's bounds, and its level by the scalar power exactly as ``compute_weights``
+    forms it.  The grid ``w`` enters on the device only (the nearest points, the fill, the sweeps; csrc/weights.hip); it
+    is accepted here so that the call reads like ``compute_weights``.  No peaks: R = 0."""
+    if len(peaks) == 0:
+        return np.empty((0, 2)), np.empty(0)
+    edges = np.array([[pk.bounds[0], pk.bounds[1]] for pk in peaks], dtype=float)           # (R, 2)
+    heights = np.abs(np.array([pk.height for pk in peaks], dtype=float))
+    top = heights.max()
+    level = np.array([np.power(top / h, expon) for h in heights])
+    return edges, level
+
+
+def pack_regions(regions):
+    """K entries ``(edges, level)`` -- or None: no regions, unit weights -- as the three arrays the library takes: the
+    region counts ``R`` (int32, K), the bounds (float64, 2 sum R) and the levels (float64, sum R), fit after fit; a
+    fit's regions start at ``np.cumsum(R)[k] - R[k]``."""
+    R = np.zeros(len(regions), dtype=np.int32)
+    edges, level = [np.empty(0)], [np.empty(0)]
+    for k, reg in enumerate(regions):
+        if reg is None:
+            continue
+        e, lv = _cabi.f64(reg[0]).reshape(-1, 2), _cabi.f64(reg[1]).ravel()
+        if len(e) != len(lv):
+            raise ValueError("regions: as many levels as pairs of bounds (entry %d)" % k)
+        R[k] = len(lv)
+        edges.append(e.ravel())
+        level.append(lv)
+    return R, np.concatenate(edges), np.concatenate(level)
+
+
+def _weight_calls(Ns):
+    """[k0, k1) ranges of at most 65535 spectra and 2^26 grid points (a lone spectrum above that is its own call; the
+    library refuses it)."""
+    k0, n = 0, len(Ns)
+    while k0 < n:
+        k1, pts = k0, 0
+        while k1 < n and k1 - k0 < _cabi._MAX_SPECTRA_PER_CALL and (k1 == k0 or pts + Ns[k1] <= _cabi.WEIGHTS_MAX_POINTS):
+            pts += Ns[k1]
+            k1 += 1
+        yield k0, k1
+        k0 = k1
+
+
+def compute_weights_many(ws, peaks_list, expon=0.5, device=0, return_pairs=False):
+    """``compute_weights(w, peaks, expon)`` for many spectra on the GPU (nmrfit_weights_build, csrc/weights.hip): the
+    list of weight arrays, each bit-identical to the host routine's, alone or in any batch.  The spectra may differ in
+    length and in their number of peaks (none: all ones); ``w`` in any order; ``expon``: a scalar or one value per
+    spectrum.  The levels are formed here (``weight_regions``), everything that touches the grid on the device.  Lists
+    of any length are cut into library calls of at most 65535 spectra and 2^26 grid points.  ``return_pairs``: also the
+    (R_k, 2) int64 arrays of every region's first and last grid index."""
+    ws = [np.ascontiguousarray(np.asarray(w, dtype=float)).ravel() for w in ws]
+    peaks_list = list(peaks_list)
+    S = len(ws)
+    if len(peaks_list) != S:
+        raise ValueError("ws and peaks_list differ in length")
+    ex = np.asarray(expon, dtype=float)
+    if ex.ndim == 0:
+        ex = np.full(S, float(ex))
+    elif ex.shape != (S,):
+        raise ValueError("expon must be a scalar or one value per spectrum (%d), got shape %s" % (S, ex.shape))
+    regions = [weight_regions(w, pk, e) for w, pk, e in zip(ws, peaks_list, ex)]
+    out, pairs = [], []
+    lib = _cabi.lib()
+    for k0, k1 in _weight_calls([len(w) for w in ws]):
+        N = np.array([len(w) for w in ws[k0:k1]], dtype=np.int64)
+        R, edges, level = pack_regions(regions[k0:k1])
+        grid = np.concatenate(ws[k0:k1])
+        weights = np.empty(grid.size)
+        first_last = np.empty((int(R.sum()), 2), dtype=np.int64)
+        _cabi.check(lib.nmrfit_weights_build(int(device), k1 - k0, _cabi.ptr(N), _cabi.ptr(grid), _cabi.ptr(R),
+                                             _cabi.ptr(edges), _cabi.ptr(level), _cabi.ptr(weights),
+                                             _cabi.ptr(first_last) if return_pairs else None))
+        noff = np.concatenate(([0], np.cumsum(N)))
+        roff = np.concatenate(([0], np.cumsum(R)))
+        for k in range(k1 - k0):
+            out.append(weights[noff[k]:noff[k + 1]])
+            pairs.append(first_last[roff[k]:roff[k + 1]])
+    return (out, pairs) if return_pairs else out
+
+
 def default_variant(N, P, fit_im=False):
     """Kernel variant ``fit`` uses when options['variant'] is absent: the far-field form
     (distant peaks' Lorentzian tails through one shared expansion per 512-point chunk, values
@@ -161,6 +247,21 @@ class FitUtility:
     def _compute_weights(self):
         return compute_weights(self.data.w, self.data.peaks, self.expon)
 
+    def _host_weights(self):
+        weights = self._compute_weights()
+        if self.dynamic_weighting is False:
+            weights = np.ones_like(weights)
+        return weights
+
+    def __getattr__(self, name):
+        # (only reached for an attribute that is missing.)  ``weights`` of a fit whose weights were built on the device
+        # (core.fit_many(device_weights=True)), or that another rank made: the host routine on first access -- bit for
+        # bit what the device plane held -- and kept from then on.
+        if name == 'weights':
+            self.weights = self._host_weights()
+            return self.weights
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def _device(self):
         """The GPU this process works on: options['device'] if given; else, with a ready
         pso.RcclExchange, the device its communicator lives on; else, in a multi-rank fit
@@ -182,12 +283,17 @@ class FitUtility:
                 self._device_note_shown = True
         return 0 if device is None else int(device)
 
-    def _plan(self):
+    def _plan(self, device_weights=False):
         """What fit() decides before anything touches the GPU (utils.py:164-181): the weights, the swarm's constants and
-        size, the seed, the kernel variant.  Shared by fit() and by core.fit_many's device-batched path."""
-        self.weights = self._compute_weights()
-        if self.dynamic_weighting is False:
-            self.weights = np.ones_like(self.weights)
+        size, the seed, the kernel variant.  Shared by fit() and by core.fit_many's device-batched path.
+        ``device_weights`` (core.fit_many): the plan carries the fit's weight regions (``weight_regions``; none with
+        ``dynamic_weighting=False``: unit weights) for a batch that builds its weights on the device, and ``weights`` is
+        left to its first access."""
+        if device_weights:
+            self.__dict__.pop('weights', None)
+            regions = weight_regions(self.data.w, self.data.peaks if self.dynamic_weighting is not False else (), self.expon)
+        else:
+            self.weights = self._host_weights()
         opt = self.options
         plan = dict(kw=dict(omega=opt.get('omega', pso.DEFAULTS['omega']), phip=opt.get('phip', pso.DEFAULTS['phip']),
                             phig=opt.get('phig', pso.DEFAULTS['phig']), minstep=opt.get('minstep', pso.DEFAULTS['minstep']),
@@ -199,6 +305,8 @@ class FitUtility:
             seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
         self.seed = seed     # (extra attribute: the seed this fit ran with -- rank 0's in a multi-rank fit)
         plan['seed'] = seed
+        if device_weights:
+            plan['regions'] = regions
         # kernel variant: by name or number, default by problem size (default_variant above)
         n_peaks = (len(self.lower) - 4) // 3
         plan['n_peaks'] = n_peaks
