@@ -158,6 +158,12 @@ PREP_SIGNATURES = {
     "nmrfit_batch_create_regions": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _INT, _INT,
                                     _c_void_pp],
 }
+# LSQ_SIGNATURES: include/nmrfit_amd_lsq.h (the least-squares pieces of a fit on the device: Jacobian, normal equations)
+LSQ_SIGNATURES = {
+    "nmrfit_jacobian": [_VP, _I32, _VP, _VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_normal_equations": [_VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
+LSQ_MAX_D = 76                    # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
 _LIB = None
@@ -260,7 +266,7 @@ def lib():
         # HIP call this library makes.  A value the user exported wins.
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
-        for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()):
+        for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

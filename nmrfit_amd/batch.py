@@ -65,6 +65,7 @@ class FitBatch:
         self._w_range = [(np.min(sp[0]), np.max(sp[0])) for sp in spectra]      # (generate: the upsampled grids' ends)
         lbs = [_cabi.f64(lo) for lo in lowers]
         ubs = [_cabi.f64(up) for up in uppers]
+        self.lowers, self.uppers = lbs, ubs
         self.D = []
         for k, (lo, up) in enumerate(zip(lbs, ubs)):
             assert len(lo) == len(up), 'Lower- and upper-bounds must be the same length'
@@ -184,6 +185,67 @@ class FitBatch:
                             real=real[roff[k]:roff[k + 1]].reshape(int(P[k]), nk),
                             imag=imag[roff[k]:roff[k + 1]].reshape(int(P[k]), nk),
                             V=f4[0], I=f4[1], u=f4[2], v=f4[3], data_V=d2[0], data_I=d2[1]))
+        return out
+
+    # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
+    def normal_equations(self, X):
+        """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``
+        would make for each fit's box, their residual rows for ALL fits in one launch over the batch's resident spectra,
+        A = J^T J and g = J^T r reduced on the device (csrc/lsq.hip), f the launch's own objective value at X[k].
+        Bit-identical to ``lsq.ResidualModel(Evaluator(spectrum), lower, upper).normal_equations(X[k])`` fit by fit, in
+        any batch.  The swarms are not touched.  D <= 76 for every fit."""
+        from . import lsq
+        if len(X) != self.K:
+            raise ValueError("FitBatch.normal_equations: one parameter vector per fit")
+        rows, cs = [], []
+        s = 1.0 / np.sqrt(self.Ns.astype(np.float64))
+        for k, x in enumerate(X):
+            x = _cabi.f64(x)
+            if x.shape != (self.D[k],):
+                raise ValueError("FitBatch.normal_equations: fit %d takes %d parameters" % (k, self.D[k]))
+            r, h = lsq.forward_rows(x, self.lowers[k], self.uppers[k])
+            rows.append(r.ravel())
+            cs.append(s[k] / h)
+        rows, cs = np.concatenate(rows), np.concatenate(cs)
+        D = np.asarray(self.D, dtype=np.int64)
+        aoff = np.concatenate(([0], np.cumsum(D * D)))
+        A = np.empty(int(aoff[-1]))
+        g = np.empty(int(self.offsets[-1]))
+        f = np.empty(self.K)
+        _cabi.check(self._lib.nmrfit_batch_normal_equations(self._h, _cabi.ptr(rows), _cabi.ptr(cs), _cabi.ptr(s), _cabi.ptr(A),
+                                                            _cabi.ptr(g), _cabi.ptr(f)))
+        return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), g[self.offsets[k]:self.offsets[k + 1]], float(f[k]))
+                for k in range(self.K)]
+
+    def polish(self, X=None, which=None, **kwargs):
+        """Least-squares refinement of the K fits in lock step (``lsq.lm_polish`` over ``normal_equations``): every
+        launch evaluates the trial points of all fits still moving.  ``X`` None: from ``best()``.  ``which``: the fits
+        to refine (default all); the others come back as they are.  Real-part objective only (fit_im=False batches).
+        Returns per fit ``(x, f)``, f the rows launch's objective value at x -- never above the start's."""
+        from . import lsq
+        start = self.best()
+        if X is None:
+            X = [x for x, _ in start]
+        X = [_cabi.f64(x) for x in X]
+        which = list(range(self.K)) if which is None else [int(k) for k in which]
+        if not which:
+            return [(x, fk) for x, (_, fk) in zip(X, start)]
+        last = [x.copy() for x in X]
+
+        def provider(trial):
+            # (the launch covers the whole batch: a fit that has stopped is evaluated where it stands and ignored)
+            full = list(last)
+            for k, x in zip(which, trial):
+                if x is not None:
+                    full[k] = x
+            got = self.normal_equations(full)
+            return [None if x is None else got[k] for k, x in zip(which, trial)]
+        Xw, fw, info = lsq.lm_polish(provider, [X[k] for k in which], [self.lowers[k] for k in which],
+                                     [self.uppers[k] for k in which], **kwargs)
+        out = [(x, fk) for x, (_, fk) in zip(X, start)]
+        for k, x, fk in zip(which, Xw, fw):
+            out[k] = (x, float(fk))
+        self.last_polish = info
         return out
 
     # -- diagnostics (include/nmrfit_amd_diag.h) ----------------------------------------------------

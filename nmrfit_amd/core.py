@@ -32,7 +32,7 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
 
 
 def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
-             **kwargs):
+             batch_polish=False, **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -74,7 +74,15 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
     * ``device_weights=True``: the error weights of the fits of a device batch (``utils.compute_weights``, the one
       O(N x P) stage the preparation thread otherwise runs per fit) are built on the GPU as part of the batch's creation
       (csrc/weights.hip; ``FitBatch(regions=...)``), bit for bit the host's, so ``params`` and ``error`` do not change.
-      ``f.weights`` of such a fit is made by the host routine on first access.  Fits that run alone take the host path."""
+      ``f.weights`` of such a fit is made by the host routine on first access.  Fits that run alone take the host path.
+    * ``batch_polish=True``: jobs with ``options['polish']`` and ``fit_im=False`` that ran in a device batch are refined
+      by ``FitBatch.polish`` while the batch is still resident -- all of them in lock step, every step one launch of
+      every fit's D + 1 residual rows and the normal equations reduced on the device (csrc/lsq.hip; ``lsq.lm_polish``),
+      D^2 + D doubles per fit and step to the host -- in place of a context, an upload and scipy's trust-region
+      iterations per fit.  Same objective, same start, another solver: ``params`` agree with the per-fit path to the
+      minimum's accuracy, not bit for bit; ``error`` is the rows launch's value at the accepted point and never above the
+      swarm's; ``generate`` reconstructs from the refined parameters.  Jobs with ``fit_im``, jobs that fell back to lone
+      fits and lone ``fit()`` keep the per-fit path."""
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     if devices is not None:
@@ -88,19 +96,22 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
         devices = [int(d) for d in devices]
         if not devices:
             raise ValueError("fit_many: no devices")
-        return _fit_many_devices(jobs, threads, batch, kwargs, devices, generate, device_weights)
+        return _fit_many_devices(jobs, threads, batch, kwargs, devices, generate, device_weights, batch_polish)
     if shard:
         from . import rendezvous
         rank, _, world = rendezvous.env_rank_world()
         if world > 1:
             return _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=channel, generate=generate,
-                                     device_weights=device_weights)
-    return _fit_many_local(jobs, threads, batch, kwargs, generate, **_flags(device_weights))
+                                     device_weights=device_weights, batch_polish=batch_polish)
+    return _fit_many_local(jobs, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
 
 
-def _flags(device_weights):
+def _flags(device_weights, batch_polish=False):
     """The opt-in arguments of _fit_many_local, passed on only when they are set."""
-    return {"device_weights": True} if device_weights else {}
+    flags = {"device_weights": True} if device_weights else {}
+    if batch_polish:
+        flags["batch_polish"] = True
+    return flags
 
 
 def _result_record(f):
@@ -121,7 +132,7 @@ def _with_device(job, shared_options, device, force=False):
 
 
 def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, local=None, generate=False,
-                      device_weights=False):
+                      device_weights=False, batch_polish=False):
     """Jobs r, r + world, ... on this rank's GPU; every rank returns every result (the other ranks' as FitUtility
     objects holding ``params`` / ``error`` / ``seed``; their ``weights`` are recomputed on demand only by ``fit``)."""
     import json
@@ -134,7 +145,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
             sys.stderr.write("nmrfit: %s\n" % note)
 
         def local(my_jobs):
-            return _fit_many_local(my_jobs, threads, batch, kwargs, generate, **_flags(device_weights))
+            return _fit_many_local(my_jobs, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
     else:
         device = None
     # the ranks meet BEFORE they fit: a mis-launched world shows at once, and the channel's connect deadline does not
@@ -165,7 +176,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
     return out
 
 
-def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, device_weights=False):
+def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, device_weights=False, batch_polish=False):
     """Job k on devices[k % len(devices)], one host thread per device (the library releases the GIL inside its calls;
     every call binds its own device), results back in job order."""
     from concurrent.futures import ThreadPoolExecutor
@@ -174,7 +185,7 @@ def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, dev
 
     def one(i):
         mine = [_with_device(jobs[k], shared, devices[i], force=True) for k in shares[i]]
-        return _fit_many_local(mine, threads, batch, kwargs, generate, **_flags(device_weights))
+        return _fit_many_local(mine, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
     out = [None] * len(jobs)
     with ThreadPoolExecutor(max_workers=len(devices)) as pool:
         for idx, res in zip(shares, pool.map(one, range(len(devices)))):
@@ -214,10 +225,11 @@ def _batch_jobs(n):
     return min(BATCH_JOBS_MAX, max(BATCH_JOBS_MIN, -(-n // PIPELINE_BATCHES)))
 
 
-def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights=False):
+def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights=False, batch_polish=False):
     from concurrent.futures import ThreadPoolExecutor
     from ._cabi import NmrfitError
     scale = 1 if generate is True else generate      # (False: no reconstruction)
+    bp = {"batch_polish": True} if batch_polish else {}      # (passed on only when set, like _flags)
     fits = []
     for job in jobs:
         args = dict(kwargs, **job)
@@ -269,7 +281,7 @@ def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights
                         fut, (fb, bfits, bplans, key, _) = inflight.popleft()
                         got = fut.result()
                         if got is None:
-                            posted.append(post.submit(_batch_collect, fb, bfits, bplans, key, scale, threads))
+                            posted.append(post.submit(_batch_collect, fb, bfits, bplans, key, scale, threads, **bp))
                         else:
                             posted.append(post.submit(_batch_store, bfits, bplans, key, got[0], got[1], got[2], scale, threads))
 
@@ -277,7 +289,7 @@ def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights
                     fb.run(key[4], key[5])                      # (maxiter, check_every)
                     if not READ_ON_RUNNER:
                         return None
-                    return _batch_read(fb, bfits, scale)        # status, best rows, reconstruction; closes the batch
+                    return _batch_read(fb, bfits, scale, **bp)  # status, best rows, reconstruction; closes the batch
 
                 def run(ready, last=False):
                     made.extend(r[0] for r in ready)
@@ -288,7 +300,7 @@ def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights
                             # the only batch of the call: nothing to overlap it with -- run and read back here, without
                             # a thread's first HIP call in the way (a 40-job list is 30 ms in all)
                             fb.run(key[4], key[5])
-                            _batch_collect(fb, bfits, bplans, key, scale, threads)
+                            _batch_collect(fb, bfits, bplans, key, scale, threads, **bp)
                             continue
                         # RUN_AT_ONCE batches are driven at the same time (threads of their own: the C calls release
                         # the GIL): while the last swarms of one batch finish -- a generation of three swarms costs a
@@ -373,20 +385,36 @@ def _fit_batch(fits, plans, key, generate=False):
     _batch_collect(fb, fits, plans, key, 1 if generate is True else generate)
 
 
-def _batch_read(fb, fits, scale=False):
+def _lsq_max_d():
+    from . import _cabi
+    return _cabi.LSQ_MAX_D
+
+
+def _batch_read(fb, fits, scale=False, batch_polish=False):
     """What is read from the device after a batch's generations: stop codes, best positions and -- ``scale`` not False --
-    the reconstruction of every fit in one launch (FitBatch.generate).  Closes the batch."""
+    the reconstruction of every fit in one launch (FitBatch.generate).  ``batch_polish``: the fits with
+    options['polish'] and fit_im=False are refined here, in lock step, from the batch's resident spectra
+    (FitBatch.polish); their entries of ``best`` are then the refined ones and _batch_store leaves them alone.
+    Closes the batch."""
     polished = sum(1 for f in fits if f.options.get('polish', False))
     with fb:
         status = fb.status()
         best = fb.best()
         results = fb.generate(scale) if scale is not False and polished < len(fits) else None
+        if batch_polish:
+            which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and not f.fit_im]
+            # (the launch covers the whole batch: one fit beyond the kernel's D leaves all of them to the per-fit path)
+            if which and max(len(f.lower) for f in fits) <= _lsq_max_d():
+                refined = fb.polish([x for x, _ in best], which=which)
+                for k in which:
+                    best[k] = refined[k]
+                    fits[k]._batch_polished = True
     return status, best, results
 
 
-def _batch_collect(fb, fits, plans, key, scale=False, threads=1):
+def _batch_collect(fb, fits, plans, key, scale=False, threads=1, batch_polish=False):
     """Read back (``_batch_read``) and store (``_batch_store``) in one go."""
-    status, best, results = _batch_read(fb, fits, scale)
+    status, best, results = _batch_read(fb, fits, scale, **({"batch_polish": True} if batch_polish else {}))
     _batch_store(fits, plans, key, status, best, results, scale, threads)
 
 
@@ -397,16 +425,18 @@ def _batch_store(fits, plans, key, status, best, results, scale=False, threads=1
     from .pso import STOP_MESSAGES
     maxiter = key[4]
     polished = [k for k, f in enumerate(fits) if f.options.get('polish', False)]
-    if polished:
+    # (refined already, with the batch still resident: fit_many(batch_polish=True), _batch_read)
+    per_fit = [k for k in polished if not getattr(fits[k], "_batch_polished", False)]
+    if per_fit:
         def refine(k):
             return fits[k]._polish(best[k][0], best[k][1], plans[k])
-        if threads > 1 and len(polished) > 1:
+        if threads > 1 and len(per_fit) > 1:
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=int(threads)) as pool:
-                refined = list(pool.map(refine, polished))
+                refined = list(pool.map(refine, per_fit))
         else:
-            refined = [refine(k) for k in polished]
-        for k, xf in zip(polished, refined):
+            refined = [refine(k) for k in per_fit]
+        for k, xf in zip(per_fit, refined):
             best[k] = xf
     for k, (f, p, st, (x, fx)) in enumerate(zip(fits, plans, status, best)):
         # (pyswarm's closing line, once per fit like the plain loop prints it)

@@ -2,6 +2,7 @@
 // life-cycle, host-pointer and device-pointer forms of the objective / residual calls,
 // device memory and HIP-event timing helpers.  No exception leaves this file.
 #include "host_call.h"
+#include "lsq_internal.h"
 #include "nmrfit_amd_diag.h"
 #include "result_internal.h"
 
@@ -420,7 +421,7 @@ int nmrfit_ctx_destroy(nmrfit_ctx *ctx)
         (void)hipStreamSynchronize(ctx->stream);
         if (ctx->stream != ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     }
-    void *bufs[] = {ctx->d_block /* wc, u, v, weights, chunk table, landing buffer */, ctx->d_X, ctx->d_f, ctx->d_partial, ctx->d_R};
+    void *bufs[] = {ctx->d_block /* wc, u, v, weights, chunk table, landing buffer */, ctx->d_X, ctx->d_f, ctx->d_partial, ctx->d_R, ctx->d_lsq};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -651,6 +652,69 @@ int nmrfit_residual_batch(nmrfit_ctx *ctx, int64_t B, int32_t P, const double *X
     if (f_out)
         NMRFIT_HIP(hipMemcpyAsync(f_out, ctx->d_f, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     NMRFIT_HIP(hipStreamSynchronize(ctx->stream));
+    return NMRFIT_OK;
+}
+
+// include/nmrfit_amd_lsq.h: the D + 1 residual rows of a forward-difference Jacobian stay on the device; what comes back
+// is J in scipy's layout, r, and / or the D x D normal equations.  One upload (rows, c, the kernel's record), the rows
+// launch, the kernels of lsq.hip, the copies back (J through the pinned staging buffers).
+int nmrfit_jacobian(nmrfit_ctx *ctx, int32_t P, const double *rows, const double *c, double s, double *J_out, double *r_out,
+                    double *A_out, double *g_out, double *f_out)
+{
+    int rc = bind(ctx);
+    if (rc != NMRFIT_OK) return rc;
+    if (!rows || !c) {
+        set_error("nmrfit_jacobian: null rows or c");
+        return NMRFIT_E_INVALID;
+    }
+    rc = check_batch(ctx, 1, P, rows, c);
+    if (rc != NMRFIT_OK) return rc;
+    const int64_t D = 4 + 3 * (int64_t)P, B = D + 1, N = ctx->N;
+    const bool sums = A_out || g_out;
+    if (sums && D > kLsqMaxD) {
+        set_error("nmrfit_jacobian: A and g need D = 4 + 3 P <= " + std::to_string(kLsqMaxD));
+        return NMRFIT_E_UNSUPPORTED;
+    }
+    if (!J_out && !r_out && !sums && !f_out) return NMRFIT_OK;
+    constexpr int64_t kJobDoubles = (sizeof(LsqJob) + sizeof(double) - 1) / sizeof(double);
+    LsqJob job{};
+    lsq_segments(N, &job.nseg, &job.seg_tiles);
+    const int64_t n_partial = sums ? job.nseg * lsq_sums(D) : 0;
+    const int64_t n_J = J_out ? N * D : 0, n_r = r_out ? N : 0, n_Ag = sums ? D * D + D : 0;
+    if ((rc = ensure(ctx, &ctx->d_X, &ctx->cap_X, B * D + D + kJobDoubles)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_f, &ctx->cap_f, B)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_R, &ctx->cap_R, B * N)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_lsq, &ctx->cap_lsq, n_J + n_r + n_partial + n_Ag + 1)) != NMRFIT_OK) return rc;
+    double *d_c = ctx->d_X + B * D, *d_job = d_c + D;
+    double *d_J = ctx->d_lsq, *d_r = d_J + n_J, *d_partial = d_r + n_r, *d_A = d_partial + n_partial, *d_g = d_A + (sums ? D * D : 0);
+    job.R = ctx->d_R;
+    job.c = d_c;
+    job.s = s;
+    job.N = N;
+    job.D = (int32_t)D;
+    job.J = J_out ? d_J : nullptr;
+    job.r = r_out ? d_r : nullptr;
+    job.partial = sums ? d_partial : nullptr;
+    job.A = sums ? d_A : nullptr;
+    job.g = sums ? d_g : nullptr;
+    hipStream_t st = ctx->stream;
+    std::vector<double> up((size_t)(B * D + D + kJobDoubles));
+    memcpy(up.data(), rows, (size_t)(B * D) * sizeof(double));
+    memcpy(up.data() + B * D, c, (size_t)D * sizeof(double));
+    memcpy(up.data() + B * D + D, &job, sizeof job);
+    // (pageable host memory: the copy has left `up` when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(ctx->d_X, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = launch_objective(ctx, B, P, ctx->d_X, ctx->d_f, ctx->d_R)) != NMRFIT_OK) return rc;
+    if (J_out || r_out || sums) {
+        rc = (D <= kLsqMaxD) ? launch_lsq(st, reinterpret_cast<const LsqJob *>(d_job), 1, (int32_t)D, sums) : launch_lsq_plain(st, job);
+        if (rc != NMRFIT_OK) return rc;
+    }
+    if (A_out) NMRFIT_HIP(hipMemcpyAsync(A_out, d_A, (size_t)(D * D) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (g_out) NMRFIT_HIP(hipMemcpyAsync(g_out, d_g, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (f_out) NMRFIT_HIP(hipMemcpyAsync(f_out, ctx->d_f, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_out && (rc = staged_d2h(ctx->device, st, r_out, d_r, (size_t)N * sizeof(double))) != NMRFIT_OK) return rc;
+    if (J_out && (rc = staged_d2h(ctx->device, st, J_out, d_J, (size_t)(N * D) * sizeof(double))) != NMRFIT_OK) return rc;
+    NMRFIT_HIP(hipStreamSynchronize(st));
     return NMRFIT_OK;
 }
 

@@ -1,0 +1,211 @@
+// lsq.hip -- the least-squares pieces of a fit on the device (include/nmrfit_amd_lsq.h): from D + 1 residual rows that
+// are already in device memory, the forward-difference Jacobian J (N x D, the layout scipy receives), the residual r, and
+// the normal equations A = J^T J, g = J^T r; plus the residual-rows launch over every fit of a resident batch.
+//
+// lsq_normal_kernel: a workgroup owns a SEGMENT of the grid (whole tiles of 64 points; at most 64 segments per fit, a
+// function of N alone).  Per tile it forms T[j][0..D) = (R[i + 1][j] - R[0][j]) * c_i and T[j][D] = R[0][j] * s in LDS --
+// the row loads coalesced along the grid, the LDS rows at an ODD pitch so that the 64 lanes of a load (64 different j)
+// hit 64 different bank pairs -- writes the tile of J as ONE contiguous run of 64 D doubles (row-major N x D: the tile's
+// rows follow each other in memory) and r, and then every thread adds the tile's 64 products to the (up to) twelve
+// entries of the upper triangle of A / of g it owns, in registers, point after point.  A and g are the same thing to
+// the kernel: g_i is the "pair" (i, D).  The per-segment sums go to memory; lsq_reduce_kernel adds them segment after
+// segment and mirrors the triangle.  Every sum has ONE order, fixed by N: no atomics, nothing depends on scheduling.
+//
+// The products are plain fp64 FMAs, not v_mfma_f64_16x16x4_f64: D = 4 + 3 P is never a multiple of 16 (76 = 4.75
+// blocks: a quarter of the last block row and column would multiply padding), the contraction is N D^2 / 2 = 47 MFLOP at
+// the C5 shape -- microseconds next to the rows launch before it, which evaluates (D + 1) N P Voigt profiles -- and
+// with scalar FMAs the order of every sum is written down in the loop below, which is what the bit-for-bit
+// requirements rest on.  
+//
+// J and r equal the host's expressions bit for bit: `(a - b) * c` has nothing added to the product, so -ffp-contract=on
+// finds nothing to fuse.
+#include "lsq_internal.h"
+#include "objective_kernel.h"
+
+namespace nmrfit {
+namespace {
+
+// entry o of a fit's sums -> the pair (a, b): the upper triangle row after row, then the D entries of g as (i, D)
+__device__ __forceinline__ void lsq_pair(int o, int D, int *a, int *b)
+{
+    const int ntri = D * (D + 1) / 2;
+    if (o >= ntri) {
+        *a = o - ntri;
+        *b = D;
+        return;
+    }
+    int row = 0, rem = o;
+    while (rem >= D - row) {
+        rem -= D - row;
+        ++row;
+    }
+    *a = row;
+    *b = row + rem;
+}
+
+__global__ __launch_bounds__(kLsqThreads) void lsq_normal_kernel(const LsqJob *__restrict__ jobs)
+{
+    extern __shared__ double T[];   // [kLsqTile][pitch]
+    const LsqJob &q = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= q.nseg) return;   // (a batch's launch is as wide as its longest grid needs)
+    const int D = q.D, pitch = (D + 1) | 1;
+    const int64_t N = q.N;
+    const int tid = threadIdx.x, jl = tid & (kLsqTile - 1), i0 = tid >> 6;
+    const bool sums = q.partial != nullptr;
+    const int nout = sums ? D * (D + 1) / 2 + D : 0;
+    int pa[kLsqAcc], pb[kLsqAcc];
+    double acc[kLsqAcc];
+#pragma unroll
+    for (int m = 0; m < kLsqAcc; ++m) {
+        const int o = tid + m * kLsqThreads;
+        pa[m] = pb[m] = 0;
+        if (o < nout) lsq_pair(o, D, &pa[m], &pb[m]);
+        acc[m] = 0.0;
+    }
+    const int64_t tiles = (N + kLsqTile - 1) / kLsqTile;
+    const int64_t t0 = (int64_t)blockIdx.x * q.seg_tiles;
+    const int64_t t1 = (t0 + q.seg_tiles < tiles) ? t0 + q.seg_tiles : tiles;
+    const double *__restrict__ R = q.R;
+    const double *__restrict__ c = q.c;
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t j0 = t * kLsqTile;
+        const int nj = (int)((N - j0 < kLsqTile) ? N - j0 : kLsqTile);
+        const bool have = jl < nj;
+        const double r0 = have ? R[j0 + jl] : 0.0;
+        for (int i = i0; i < D; i += kLsqThreads / kLsqTile) {
+            const double ri = have ? R[(int64_t)(i + 1) * N + j0 + jl] : 0.0;
+            T[jl * pitch + i] = (ri - r0) * c[i];
+        }
+        if (i0 == 0) T[jl * pitch + D] = r0 * q.s;
+        __syncthreads();
+        if (q.J) {   // rows j0 .. j0 + nj of the row-major N x D matrix: nj D consecutive doubles
+            double *__restrict__ Jt = q.J + j0 * D;
+            for (int e = tid; e < nj * D; e += kLsqThreads) {
+                const int jj = e / D;
+                Jt[e] = T[jj * pitch + (e - jj * D)];
+            }
+        }
+        if (q.r && i0 == 0 && have) q.r[j0 + jl] = T[jl * pitch + D];
+        if (sums) {
+            for (int jj = 0; jj < nj; ++jj) {
+                const double *row = T + jj * pitch;
+#pragma unroll
+                for (int m = 0; m < kLsqAcc; ++m) acc[m] = __builtin_fma(row[pa[m]], row[pb[m]], acc[m]);
+            }
+        }
+        __syncthreads();
+    }
+    if (sums) {
+        double *__restrict__ out = q.partial + (int64_t)blockIdx.x * nout;
+#pragma unroll
+        for (int m = 0; m < kLsqAcc; ++m) {
+            const int o = tid + m * kLsqThreads;
+            if (o < nout) out[o] = acc[m];
+        }
+    }
+}
+
+// the segments' sums one after the other, segment 0 first; A comes back whole (both triangles from the same sum)
+__global__ __launch_bounds__(kLsqThreads) void lsq_reduce_kernel(const LsqJob *__restrict__ jobs)
+{
+    const LsqJob &q = jobs[blockIdx.x];
+    if (!q.partial) return;
+    const int D = q.D, nout = D * (D + 1) / 2 + D;
+    for (int o = threadIdx.x; o < nout; o += kLsqThreads) {
+        double sum = 0.0;
+        for (int sgm = 0; sgm < q.nseg; ++sgm) sum += q.partial[(int64_t)sgm * nout + o];
+        int a, b;
+        lsq_pair(o, D, &a, &b);
+        if (b == D) {
+            if (q.g) q.g[a] = sum;
+        } else if (q.A) {
+            q.A[a * D + b] = sum;
+            q.A[b * D + a] = sum;
+        }
+    }
+}
+
+// J and r of one fit of any D, element by element
+__global__ __launch_bounds__(kLsqThreads) void lsq_jacobian_plain_kernel(LsqJob q)
+{
+    const int64_t N = q.N, D = q.D;
+    const int64_t stride = (int64_t)gridDim.x * kLsqThreads;
+    for (int64_t e = (int64_t)blockIdx.x * kLsqThreads + threadIdx.x; e < N * D; e += stride) {
+        const int64_t j = e / D, i = e - j * D;
+        if (q.J) q.J[e] = (q.R[(i + 1) * N + j] - q.R[j]) * q.c[i];
+        if (q.r && i == 0) q.r[j] = q.R[j] * q.s;
+    }
+}
+
+// Residual rows of every fit of a resident batch: workgroup b belongs to fit b / blocks_per_fit, wave = parameter row,
+// one segment (the wave walks the fit's whole grid and writes f itself, block sums in grid order).  The body is the lone
+// residual kernel's -- objective_body<DEFAULT, WRITE_R> -- on the fit's own block structure, which follows from its N
+// alone: rows and f are what nmrfit_residual_batch gives on a context of the same spectrum, bit for bit.
+__global__ __launch_bounds__(kWave *kWavesPerBlock, objective_min_waves(NMRFIT_VARIANT_DEFAULT, 0)) void residual_rows_batch_kernel(
+    const RowsFit *__restrict__ fits, int blocks_per_fit, const unsigned aux_off)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    __shared__ double wsums[kWsumsCount];
+    const int fit = (int)(blockIdx.x / (unsigned)blocks_per_fit);
+    const int64_t lblock = (int64_t)(blockIdx.x - (unsigned)fit * (unsigned)blocks_per_fit);
+    const RowsFit &d = fits[fit];
+    if (lblock * kWavesPerBlock >= d.S) return;   // (a fit with fewer rows than the batch's largest: whole workgroups idle)
+    if (threadIdx.x == 0) wsums[2 * kMaxBlocks + 1] = 0.0;   // no personal bests here
+    const int64_t g = lblock * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const PsoFused none{};
+    objective_body<NMRFIT_VARIANT_DEFAULT, true, 0, kWavesPerBlock>(lds_raw, g, lblock, d.wc, d.u, d.v, d.wt, d.chunk, d.X, d.S, d.P, d.N,
+                                                                   d.w0, d.wspan, 1, d.seg_len, d.blk_chunks, d.n_blocks, d.n_blocks,
+                                                                   d.lane_step, d.rec_devk, d.f, d.R, nullptr, none, aux_off, wsums);
+}
+
+}  // namespace
+
+int launch_lsq(hipStream_t st, const LsqJob *d_jobs, int32_t K, int32_t Dmax, bool sums)
+{
+    if (K <= 0) return NMRFIT_OK;
+    if (Dmax > kLsqMaxD) {
+        set_error("normal equations: D = 4 + 3 P above " + std::to_string(kLsqMaxD));
+        return NMRFIT_E_UNSUPPORTED;
+    }
+    const size_t lds = (size_t)kLsqTile * (size_t)((Dmax + 1) | 1) * sizeof(double);
+    hipLaunchKernelGGL(lsq_normal_kernel, dim3((unsigned)kLsqMaxSegments, (unsigned)K), dim3(kLsqThreads), lds, st, d_jobs);
+    NMRFIT_HIP(hipGetLastError());
+    if (sums) {
+        hipLaunchKernelGGL(lsq_reduce_kernel, dim3((unsigned)K), dim3(kLsqThreads), 0, st, d_jobs);
+        NMRFIT_HIP(hipGetLastError());
+    }
+    return NMRFIT_OK;
+}
+
+int launch_lsq_plain(hipStream_t st, const LsqJob &job)
+{
+    const int64_t n = job.N * job.D;
+    if (n <= 0) return NMRFIT_OK;
+    const int64_t blocks = std::min<int64_t>((n + kLsqThreads - 1) / kLsqThreads, 4096);
+    hipLaunchKernelGGL(lsq_jacobian_plain_kernel, dim3((unsigned)blocks), dim3(kLsqThreads), 0, st, job);
+    NMRFIT_HIP(hipGetLastError());
+    return NMRFIT_OK;
+}
+
+bool rows_batch_lds(int32_t Pmax, size_t *lds, unsigned *aux_off)
+{
+    int v = NMRFIT_VARIANT_DEFAULT;
+    *lds = objective_lds(NMRFIT_VARIANT_DEFAULT, Pmax, true, 0, &v, aux_off, kWavesPerBlock, kWavesPerBlock, 0);
+    return v == NMRFIT_VARIANT_DEFAULT && *lds + kObjectiveStaticLds + 16 <= 160 * 1024;
+}
+
+int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off)
+{
+    if (K <= 0 || Smax <= 0) return NMRFIT_OK;
+    const int64_t blocks_per_fit = (Smax + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (blocks_per_fit * (int64_t)K > 0x7fffffffLL) {
+        set_error("batch too large for one launch");
+        return NMRFIT_E_INVALID;
+    }
+    hipLaunchKernelGGL(residual_rows_batch_kernel, dim3((unsigned)(blocks_per_fit * K)), dim3(kWave * kWavesPerBlock), lds, st, d_fits,
+                       (int)blocks_per_fit, aux_off);
+    NMRFIT_HIP(hipGetLastError());
+    return NMRFIT_OK;
+}
+
+}  // namespace nmrfit

@@ -1,0 +1,64 @@
+// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), cabi.hip (nmrfit_jacobian) and batch.hip
+// (nmrfit_batch_normal_equations): the per-fit records the kernels read and the launches.
+#pragma once
+#include "nmrfit_amd_lsq.h"
+#include "nmrfit_internal.h"
+
+namespace nmrfit {
+
+constexpr int kLsqTile = NMRFIT_LSQ_TILE;            // grid points per tile
+constexpr int kLsqMaxSegments = NMRFIT_LSQ_MAX_SEGMENTS;
+constexpr int kLsqMaxD = NMRFIT_LSQ_MAX_D;
+constexpr int kLsqThreads = 256;
+constexpr int kLsqAcc = 12;                          // sums per thread: 256 x 12 >= 76 x 77 / 2 + 76
+static_assert(kLsqThreads * kLsqAcc >= kLsqMaxD * (kLsqMaxD + 1) / 2 + kLsqMaxD, "accumulators for the largest D");
+
+// One fit of a normal-equations launch.  R: its D + 1 residual rows, N doubles each, in plain grid order.
+struct LsqJob {
+    const double *R;
+    const double *c;       // D factors s / h_i
+    double s;
+    int64_t N;
+    int32_t D;
+    int32_t nseg;          // workgroups (segments of the grid) of this fit: a function of N alone
+    int32_t seg_tiles;     // tiles per segment
+    int32_t pad;
+    double *J;             // N x D row-major, or null
+    double *r;             // N, or null
+    double *partial;       // nseg x (D (D + 1) / 2 + D), or null: no sums
+    double *A;             // D x D
+    double *g;             // D
+};
+
+// the segments of a grid of N points: at most kLsqMaxSegments, whole tiles each
+inline void lsq_segments(int64_t N, int32_t *nseg, int32_t *seg_tiles)
+{
+    const int64_t tiles = (N + kLsqTile - 1) / kLsqTile;
+    const int64_t per = (tiles + kLsqMaxSegments - 1) / kLsqMaxSegments;
+    *seg_tiles = (int32_t)per;
+    *nseg = (int32_t)((tiles + per - 1) / per);
+}
+inline int64_t lsq_sums(int64_t D) { return D * (D + 1) / 2 + D; }
+
+// J, r and -- where a job has `partial` -- A and g of K fits (jobs: device memory), on `st`.  Dmax <= kLsqMaxD.
+int launch_lsq(hipStream_t st, const LsqJob *d_jobs, int32_t K, int32_t Dmax, bool sums);
+// J and r alone for one fit of any D (no LDS tile): what nmrfit_jacobian runs beyond kLsqMaxD
+int launch_lsq_plain(hipStream_t st, const LsqJob &job);
+
+// One fit of a residual-rows launch over a batch's resident spectra: the grid as BatchFit holds it, S parameter rows
+// X [S x D], their objective values f [S] and residual rows R [S x N].
+struct RowsFit {
+    const double *wc, *u, *v, *wt;
+    const double2 *chunk;
+    double w0, wspan, lane_step, rec_devk;
+    const double *X;
+    double *f;
+    double *R;
+    int64_t N, seg_len, S;
+    int32_t P, blk_chunks, n_blocks, pad;
+};
+// false: these peak counts leave the kernel's LDS records no room
+bool rows_batch_lds(int32_t Pmax, size_t *lds, unsigned *aux_off);
+int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off);
+
+}  // namespace nmrfit

@@ -119,6 +119,8 @@ struct nmrfit_ctx {
     int64_t cap_partial = 0;
     double *d_R = nullptr;
     int64_t cap_R = 0;
+    double *d_lsq = nullptr;     // nmrfit_jacobian: J, r, the segments' sums, A, g
+    int64_t cap_lsq = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int variant = NMRFIT_VARIANT_DEFAULT;
     int fit_im = 0;              // 0 real only; 1 reference-compatible fit_im=True; 2 all-peak imaginary model

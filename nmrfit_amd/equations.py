@@ -167,6 +167,29 @@ class Evaluator:
                                                     _cabi.ptr(f)))
         return (R, f) if return_f else R
 
+    def jacobian(self, rows, c, s, J=False, r=False, normal=False):
+        """``nmrfit_jacobian`` (include/nmrfit_amd_lsq.h): the D + 1 residual rows of the parameter rows ``rows`` stay on
+        the device; returns a dict with what was asked for -- ``J`` [N, D] = (R[i + 1] - R[0]) * c_i (row-major, the
+        layout scipy takes), ``r`` [N] = R[0] * s, ``A`` [D, D] = J^T J and ``g`` [D] = J^T r (``normal``) -- and ``f``,
+        the objective value of row 0."""
+        rows, P = self._as_batch(rows)
+        D = rows.shape[1]
+        c = _cabi.f64(c)
+        if rows.shape[0] != D + 1 or c.shape != (D,):
+            raise ValueError("jacobian: rows must be (D + 1) x D and c have D entries")
+        out = dict(f=np.empty(1))
+        if J:
+            out["J"] = np.empty((self.N, D))
+        if r:
+            out["r"] = np.empty(self.N)
+        if normal:
+            out["A"], out["g"] = np.empty((D, D)), np.empty(D)
+        _cabi.check(self._lib.nmrfit_jacobian(self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s), _cabi.ptr(out.get("J")),
+                                              _cabi.ptr(out.get("r")), _cabi.ptr(out.get("A")), _cabi.ptr(out.get("g")),
+                                              _cabi.ptr(out["f"])))
+        out["f"] = float(out["f"][0])
+        return out
+
     # -- device-resident helpers (bench / swarm) ------------------------------------------
     def dev_alloc(self, nbytes):
         p = ctypes.c_void_p()

@@ -11,12 +11,47 @@ the D+1 parameter rows a forward-difference Jacobian needs.
 ``least_squares`` hands both to scipy.optimize.least_squares (trust-region reflective, box
 bounds); ``polish`` refines a swarm result.  scipy runs on the host; every residual and
 Jacobian column comes from the GPU.
+
+The Jacobian is formed on the device (``nmrfit_jacobian``, csrc/lsq.hip): the D + 1 residual rows never
+leave it, J arrives in the N x D layout scipy takes, bit for bit the expression above.  The same kernel
+reduces the normal equations A = J^T J, g = J^T fun there (``ResidualModel.normal_equations``; for every fit
+of a device batch in one go: ``FitBatch.normal_equations``), D^2 + D doubles per fit instead of N D.
+``lm_polish`` is the small host loop over such D x D systems that refines K fits in lock step
+(``FitBatch.polish``, ``fit_many(batch_polish=True)``); ``normal_equations_host`` states the same quantities
+in numpy.
 """
 import numpy as np
 
 from . import _cabi
 
 _SQRT_EPS = float(np.sqrt(np.finfo(np.float64).eps))
+
+
+def forward_rows(x, lower=None, upper=None, rel_step=_SQRT_EPS):
+    """The D + 1 parameter rows of a forward-difference Jacobian at ``x`` and the steps actually taken after
+    rounding: h_i = rel_step*max(1,|x_i|), flipped where x_i + h_i would leave the box (scipy's '2-point' rule)."""
+    x = np.asarray(x, dtype=np.float64)
+    h = rel_step * np.maximum(1.0, np.abs(x))
+    if upper is not None:
+        flip = x + h > upper
+        if lower is not None:
+            flip &= (x - h >= lower)
+        h = np.where(flip, -h, h)
+    rows = np.tile(x, (x.size + 1, 1))
+    idx = np.arange(x.size)
+    rows[idx + 1, idx] += h
+    return rows, rows[idx + 1, idx] - x
+
+
+def normal_equations_host(R, c, s):
+    """What csrc/lsq.hip computes from the D + 1 residual rows ``R`` [(D + 1) x N], the factors ``c`` (s / h_i) and
+    ``s`` = 1/sqrt(N), in numpy: ``(A, g, J, r)`` with r = R[0]*s, J[j, i] = (R[i + 1][j] - R[0][j])*c_i [N x D],
+    A = J^T J, g = J^T r.  (J and r are the device's bit for bit; A and g differ in summation order.)"""
+    R = np.asarray(R, dtype=np.float64)
+    c = np.asarray(c, dtype=np.float64)
+    r = R[0] * s
+    J = np.ascontiguousarray(((R[1:] - R[0]) * c[:, None]).T)
+    return J.T @ J, J.T @ r, J, r
 
 
 class ResidualModel:
@@ -49,20 +84,22 @@ class ResidualModel:
         return h
 
     def rows(self, x):
-        x = np.asarray(x, dtype=np.float64)
-        h = self.steps(x)
-        rows = np.tile(x, (x.size + 1, 1))
-        idx = np.arange(x.size)
-        rows[idx + 1, idx] += h
-        # the step actually taken after rounding
-        return rows, rows[idx + 1, idx] - x
+        return forward_rows(x, self.lower, self.upper, self.rel_step)
 
     def jac(self, x):
+        """[fun(x + h_i e_i) - fun(x)] / h_i as N x D: one launch of the D + 1 residual rows, J formed on the
+        device from them (csrc/lsq.hip) -- the bits of ``(R[1:] - R[0]) * (scale / h)`` transposed."""
         self.n_jac += 1
         rows, h = self.rows(x)
-        R = self.ev.residual_batch(rows)                    # one launch: (D+1) x N
-        J = (R[1:] - R[0]) * (self._scale / h[:, None])    # D x N
-        return np.ascontiguousarray(J.T)                    # N x D
+        return self.ev.jacobian(rows, self._scale / h, self._scale, J=True)["J"]
+
+    def normal_equations(self, x):
+        """``(A, g, f)`` at x: A = J^T J [D x D], g = J^T fun(x) [D] reduced on the device in a fixed order, and f the
+        objective value the same launch returns for x.  D <= 76."""
+        self.n_jac += 1
+        rows, h = self.rows(x)
+        out = self.ev.jacobian(rows, self._scale / h, self._scale, normal=True)
+        return out["A"], out["g"], out["f"]
 
     def objective(self, x):
         return float(np.linalg.norm(self.fun(x)))
@@ -96,3 +133,122 @@ def polish(evaluator, x_swarm, lower, upper, fit_im=False, **kwargs):
     if f1 <= f0:
         return res.x, f1, res
     return x_swarm, f0, res
+
+
+def rows_provider(residuals, lowers, uppers, rel_step=_SQRT_EPS):
+    """A ``provider`` for ``lm_polish`` from K callables ``residuals[k](rows) -> (R [(D + 1) x N], f [D + 1])`` (a
+    host restatement of the residual, an ``Evaluator.residual_batch(..., return_f=True)``): rows and steps as ``ResidualModel`` makes them, the
+    normal equations by ``normal_equations_host``."""
+    def provider(X):
+        out = []
+        for k, x in enumerate(X):
+            if x is None:
+                out.append(None)
+                continue
+            rows, h = forward_rows(x, lowers[k], uppers[k], rel_step)
+            R, f = residuals[k](rows)
+            s = 1.0 / np.sqrt(R.shape[1])
+            A, g, _, _ = normal_equations_host(R, s / h, s)
+            out.append((A, g, float(f[0])))
+        return out
+    return provider
+
+
+def _lm_step(A, g, x, lower, upper, scale, lam):
+    """One damped step of a box-bounded fit in scaled variables: variables on a bound whose descent direction points
+    outward are frozen; (A' + lam diag(A')) d = -g' by Cholesky over the free ones.  None when the factorisation fails
+    (the caller raises lam) or nothing is free."""
+    free = ~(((x <= lower) & (g > 0.0)) | ((x >= upper) & (g < 0.0)))
+    if not free.any():
+        return None
+    d = scale[free]
+    As = A[np.ix_(free, free)] * d[:, None] * d[None, :]
+    gs = g[free] * d
+    diag = np.diag(As).copy()
+    diag[~(diag > 0.0)] = 1.0
+    try:
+        L = np.linalg.cholesky(As + lam * np.diag(diag))
+    except np.linalg.LinAlgError:
+        return None
+    step = np.linalg.solve(L.T, np.linalg.solve(L, -gs))
+    if not np.all(np.isfinite(step)):
+        return None
+    delta = np.zeros_like(x)
+    delta[free] = step * d
+    return delta
+
+
+def lm_polish(provider, X0, lowers, uppers, max_launches=30, lam0=1e-3, up=10.0, down=10.0, ftol=1e-12):
+    """Levenberg-Marquardt on K independent box-bounded least-squares problems in lock step, from device-made (or any)
+    normal equations.  ``provider(X)`` takes a list of K parameter vectors (None for a fit that has stopped) and
+    returns, per entry that is not None, ``(A, g, f)`` at it: A = J^T J, g = J^T r, f = ||r||.  One call evaluates the
+    trial points of every active fit -- and brings their A and g, so an accepted point needs no second call.
+
+    Per fit: variables scaled by max(upper - lower, 1e-12) (``least_squares``'s x_scale); a variable on a bound with -g
+    pointing outward is frozen for the step; the step solves (A + lam diag(A)) d = -g by Cholesky, a failed
+    factorisation raises lam; the trial point is clip(x + d); f' < f accepts (lam /= down), else x stays (lam *= up).  A
+    fit stops on a relative decrease below ``ftol``, on lam > 1e12, or with the budget of ``max_launches`` provider
+    calls.  f never rises: the result is never worse than the start.
+
+    Returns ``(X, f, info)``: K vectors, K values, and a dict with ``launches``, per fit ``accepted`` and ``stop``
+    ("ftol", "lambda", "budget", "frozen") and ``history`` (per fit, f after every launch it took part in)."""
+    K = len(X0)
+    lowers = [np.asarray(lo, dtype=np.float64) for lo in lowers]
+    uppers = [np.asarray(up_, dtype=np.float64) for up_ in uppers]
+    scales = [np.maximum(hi - lo, 1e-12) for lo, hi in zip(lowers, uppers)]
+    X = [np.clip(np.asarray(x, dtype=np.float64), lo, hi) for x, lo, hi in zip(X0, lowers, uppers)]
+    got = provider(list(X))
+    launches = 1
+    A = [np.array(q[0]) for q in got]
+    g = [np.array(q[1]) for q in got]
+    f = [float(q[2]) for q in got]
+    lam = [float(lam0)] * K
+    stop = [None] * K
+    accepted = [0] * K
+    history = [[fk] for fk in f]
+    active = list(range(K))
+    while active:
+        if launches >= max_launches:
+            for k in active:
+                stop[k] = "budget"
+            break
+        trial = [None] * K
+        for k in list(active):
+            delta = None
+            while delta is None:
+                delta = _lm_step(A[k], g[k], X[k], lowers[k], uppers[k], scales[k], lam[k])
+                if delta is None:
+                    free = ~(((X[k] <= lowers[k]) & (g[k] > 0.0)) | ((X[k] >= uppers[k]) & (g[k] < 0.0)))
+                    if not free.any():
+                        stop[k] = "frozen"
+                        break
+                    lam[k] *= up
+                    if lam[k] > 1e12:
+                        stop[k] = "lambda"
+                        break
+            if delta is None:
+                active.remove(k)
+                continue
+            trial[k] = np.clip(X[k] + delta, lowers[k], uppers[k])
+        if not active:
+            break
+        got = provider(trial)
+        launches += 1
+        for k in list(active):
+            A1, g1, f1 = got[k]
+            f1 = float(f1)
+            if f1 < f[k]:
+                gain = (f[k] - f1) / max(f[k], 1e-300)
+                X[k], A[k], g[k], f[k] = trial[k], np.array(A1), np.array(g1), f1
+                accepted[k] += 1
+                lam[k] /= down
+                if gain < ftol:
+                    stop[k] = "ftol"
+            else:
+                lam[k] *= up
+                if lam[k] > 1e12:
+                    stop[k] = "lambda"
+            history[k].append(f[k])
+            if stop[k] is not None:
+                active.remove(k)
+    return X, np.array(f), dict(launches=launches, accepted=accepted, stop=stop, history=history)
