@@ -85,11 +85,7 @@ class FitBatch:
         upper = np.concatenate(ubs)
         if seeds is None:
             seeds = np.random.SeedSequence().generate_state(K, dtype=np.uint64)
-
-        def per_fit(x):
-            a = np.broadcast_to(np.asarray(x, dtype=np.float64), (K,))
-            return a
-        om, pp, pg, ms, mf = (per_fit(x) for x in (omega, phip, phig, minstep, minfunc))
+        om, pp, pg, ms, mf = (np.broadcast_to(np.asarray(x, dtype=np.float64), (K,)) for x in (omega, phip, phig, minstep, minfunc))
         self.minstep, self.minfunc = ms.copy(), mf.copy()
         self.seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
         prm = (_cabi.PsoParams * K)()

@@ -4,9 +4,13 @@ value, executed on the MI355X.  ``load`` (instrument file parsing through nmrglu
 core.py:9-61) is outside the hot-path scope: build a ``Data``-like object (attributes
 w, u, v, peaks) with the reference package or ``nmrfit_amd.synth`` and pass it in.
 """
+import collections
+import typing
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
-from . import utils
+from . import _cabi, utils
 
 
 def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, processes=1, summary=True,
@@ -85,6 +89,7 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       fits and lone ``fit()`` keep the per-fit path."""
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
+    call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights), bool(batch_polish))
     if devices is not None:
         if shard:
             raise ValueError("fit_many: shard=True divides the jobs over PROCESSES, devices=[...] over the GPUs of this "
@@ -96,22 +101,23 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
         devices = [int(d) for d in devices]
         if not devices:
             raise ValueError("fit_many: no devices")
-        return _fit_many_devices(jobs, threads, batch, kwargs, devices, generate, device_weights, batch_polish)
+        return _fit_many_devices(jobs, call, devices)
     if shard:
         from . import rendezvous
         rank, _, world = rendezvous.env_rank_world()
         if world > 1:
-            return _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=channel, generate=generate,
-                                     device_weights=device_weights, batch_polish=batch_polish)
-    return _fit_many_local(jobs, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
+            return _fit_many_sharded(jobs, call, rank, world, channel=channel)
+    return _fit_many_local(jobs, call)
 
 
-def _flags(device_weights, batch_polish=False):
-    """The opt-in arguments of _fit_many_local, passed on only when they are set."""
-    flags = {"device_weights": True} if device_weights else {}
-    if batch_polish:
-        flags["batch_polish"] = True
-    return flags
+class _Call(typing.NamedTuple):
+    """What one fit_many call asked for: built once by fit_many, passed on unchanged."""
+    threads: int
+    batch: bool
+    kwargs: dict                 # fit's keyword arguments, shared by the jobs
+    scale: object                # ``generate``: False (no reconstruction), or generate_result's scale (True -> 1)
+    device_weights: bool
+    batch_polish: bool
 
 
 def _result_record(f):
@@ -131,8 +137,7 @@ def _with_device(job, shared_options, device, force=False):
     return dict(job, options=opts)
 
 
-def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, local=None, generate=False,
-                      device_weights=False, batch_polish=False):
+def _fit_many_sharded(jobs, call, rank, world, channel=None, local=None):
     """Jobs r, r + world, ... on this rank's GPU; every rank returns every result (the other ranks' as FitUtility
     objects holding ``params`` / ``error`` / ``seed``; their ``weights`` are recomputed on demand only by ``fit``)."""
     import json
@@ -145,7 +150,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
             sys.stderr.write("nmrfit: %s\n" % note)
 
         def local(my_jobs):
-            return _fit_many_local(my_jobs, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
+            return _fit_many_local(my_jobs, call)
     else:
         device = None
     # the ranks meet BEFORE they fit: a mis-launched world shows at once, and the channel's connect deadline does not
@@ -154,7 +159,7 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
     if own:
         channel = rendezvous.Channel()
     try:
-        shared = kwargs.get("options") or {}
+        shared = call.kwargs.get("options") or {}
         done = local([_with_device(jobs[i], shared, device) if device is not None else jobs[i] for i in mine])
         # (JSON, not pickle: what arrives from another rank is data, never code; repr round-trips a float64 exactly)
         parts = channel.all_gather(json.dumps([[i, _result_record(f)] for i, f in zip(mine, done)]).encode())
@@ -169,23 +174,21 @@ def _fit_many_sharded(jobs, threads, batch, kwargs, rank, world, channel=None, l
             continue
         for i, rec in json.loads(blob.decode()):
             job = jobs[i]
-            args = {k: v for k, v in dict(kwargs, **job).items() if k not in ("data", "lower", "upper")}
+            args = {k: v for k, v in dict(call.kwargs, **job).items() if k not in ("data", "lower", "upper")}
             f = utils.FitUtility(job["data"], job["lower"], job["upper"], **args)
             f.params, f.error, f.seed = np.array(rec["params"]), rec["error"], rec["seed"]
             out[i] = f
     return out
 
 
-def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, device_weights=False, batch_polish=False):
+def _fit_many_devices(jobs, call, devices):
     """Job k on devices[k % len(devices)], one host thread per device (the library releases the GIL inside its calls;
     every call binds its own device), results back in job order."""
-    from concurrent.futures import ThreadPoolExecutor
     shares = [list(range(i, len(jobs), len(devices))) for i in range(len(devices))]
-    shared = kwargs.get("options") or {}
+    shared = call.kwargs.get("options") or {}
 
     def one(i):
-        mine = [_with_device(jobs[k], shared, devices[i], force=True) for k in shares[i]]
-        return _fit_many_local(mine, threads, batch, kwargs, generate, **_flags(device_weights, batch_polish))
+        return _fit_many_local([_with_device(jobs[k], shared, devices[i], force=True) for k in shares[i]], call)
     out = [None] * len(jobs)
     with ThreadPoolExecutor(max_workers=len(devices)) as pool:
         for idx, res in zip(shares, pool.map(one, range(len(devices)))):
@@ -194,9 +197,7 @@ def _fit_many_devices(jobs, threads, batch, kwargs, devices, generate=False, dev
     return out
 
 
-def _cabi_device_count():
-    from . import _cabi
-    return _cabi.device_count()
+_cabi_device_count = _cabi.device_count      # (under a name of core's own: the CPU tests replace it)
 
 
 # Jobs per device batch in fit_many.  From ~40 default-size fits on a batch holds the MI355X's issue rate (DESIGN.md
@@ -211,12 +212,12 @@ BATCH_JOBS_MIN, BATCH_JOBS_MAX, PIPELINE_BATCHES = 40, 200, 4
 # ... 411 for default fits) and the batch's last generations hold a few swarms each, at a launch's latency; a second
 # batch running beside it fills the device meanwhile: 4 batches of 50 default fits 93.7 -> 82.4 ms (2134 -> 2427 fits/s
 # on the device), three at a time 79.8 (tools/concurrent_batches.py, profiles/r06/concurrent_batches.txt).
-RUN_AT_ONCE = 2
 # End to end (tools/pipeline_ab.py, profiles/r06/fit_many_pipeline_ab.txt; one box, best of three): 200 default jobs with
 # pyswarm's rule 1924 -> 2038 fits/s, 1000 jobs 2349 -> 2405 -- less than on the device alone, the rest of the call being
 # the first batch's preparation and the last one's read-back; with the reconstruction 1707 -> 1728 / 2146 -> 2120 (noise).
-# (measured and not kept: the first batch of a list cut in two halves to start the device sooner -- no difference.)
-READ_ON_RUNNER = False    # A/B knob: the read-back on the thread that ran the batch instead of the storing thread (same rates)
+# (measured and not kept: the first batch of a list cut in two halves to start the device sooner -- no difference; the
+# read-back on the thread that ran the batch instead of the storing thread -- same rates, same profile file.)
+RUN_AT_ONCE = 2
 
 
 def _batch_jobs(n):
@@ -225,230 +226,222 @@ def _batch_jobs(n):
     return min(BATCH_JOBS_MAX, max(BATCH_JOBS_MIN, -(-n // PIPELINE_BATCHES)))
 
 
-def _fit_many_local(jobs, threads, batch, kwargs, generate=False, device_weights=False, batch_polish=False):
-    from concurrent.futures import ThreadPoolExecutor
-    from ._cabi import NmrfitError
-    scale = 1 if generate is True else generate      # (False: no reconstruction)
-    bp = {"batch_polish": True} if batch_polish else {}      # (passed on only when set, like _flags)
+class _Batch:
+    """One device batch of a fit_many call: the FitBatch ``fb``, its ``fits`` and their ``plans``, the BatchKey they
+    share and their places ``idx`` in the job list.  create, run, read, store -- or close."""
+
+    def __init__(self, fb, fits, plans, key, idx):
+        self.fb, self.fits, self.plans, self.key, self.idx = fb, fits, plans, key, idx
+
+    @classmethod
+    def create(cls, fits, plans, key, idx):
+        """The device state of one batch (spectra, weights, boxes, swarms) -- everything up to the first launch."""
+        from .batch import FitBatch
+        swarmsize = [int(p['swarmsize']) for p in plans]
+        # (all or nothing: the plans of one fit_many call either all carry their regions -- device_weights -- or none does)
+        regions = [p['regions'] for p in plans] if all('regions' in p for p in plans) else None
+        if regions is None:
+            spectra = [(f.data.w, f.data.u, f.data.v, f.weights) for f in fits]
+        else:
+            spectra = [(f.data.w, f.data.u, f.data.v) for f in fits]
+        kw = {name: [p['kw'][name] for p in plans] for name in ("omega", "phip", "phig", "minstep", "minfunc")}
+        fb = FitBatch(spectra, [f.lower for f in fits], [f.upper for f in fits], swarmsize=swarmsize,
+                      seeds=[p['seed'] for p in plans], variant=key.variant, fit_im=key.fit_im, device=key.device,
+                      regions=regions, **kw)
+        return cls(fb, fits, plans, key, idx)
+
+    def run(self):
+        self.fb.run(self.key.maxiter, self.key.check_every)
+
+    def close(self):
+        self.fb.close()
+
+    def read(self, call):
+        """What is read from the device after the batch's generations: stop codes, best positions and -- ``call.scale``
+        not False -- the reconstruction of every fit in one launch (FitBatch.generate).  ``call.batch_polish``: the fits
+        with options['polish'] and fit_im=False are refined here, in lock step, from the batch's resident spectra
+        (FitBatch.polish); their entries of ``best`` are then the refined ones and their indices come back as
+        ``refined``: store leaves them alone.  Closes the batch.  Returns (refined, status, best, results)."""
+        fits, fb, refined = self.fits, self.fb, set()
+        polished = sum(1 for f in fits if f.options.get('polish', False))
+        try:
+            status = fb.status()
+            best = fb.best()
+            results = fb.generate(call.scale) if call.scale is not False and polished < len(fits) else None
+            if call.batch_polish:
+                which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and not f.fit_im]
+                # (the launch covers the whole batch: one fit beyond the kernel's D leaves all of them to the per-fit path)
+                if which and max(len(f.lower) for f in fits) <= _cabi.LSQ_MAX_D:
+                    new = fb.polish([x for x, _ in best], which=which)
+                    for k in which:
+                        best[k] = new[k]
+                    refined = set(which)
+        finally:
+            fb.close()
+        return refined, status, best, results
+
+    def store(self, call, refined, status, best, results):
+        """The batch's results into the FitUtility objects (what FitUtility.fit and generate_result leave behind).  Fits
+        with options['polish'] that read has not ``refined`` are refined first (FitUtility._polish, ``call.threads`` at a
+        time); every polished fit is reconstructed from its refined parameters."""
+        from .pso import STOP_MESSAGES
+        fits, plans, scale = self.fits, self.plans, call.scale
+        polished = [k for k, f in enumerate(fits) if f.options.get('polish', False)]
+        per_fit = [k for k in polished if k not in refined]
+        if per_fit:
+            def refine(k):
+                return fits[k]._polish(best[k][0], best[k][1], plans[k])
+            if call.threads > 1 and len(per_fit) > 1:
+                with ThreadPoolExecutor(max_workers=int(call.threads)) as pool:
+                    new = list(pool.map(refine, per_fit))
+            else:
+                new = [refine(k) for k in per_fit]
+            for k, xf in zip(per_fit, new):
+                best[k] = xf
+        for k, (f, p, st, (x, fx)) in enumerate(zip(fits, plans, status, best)):
+            # (pyswarm's closing line, once per fit like the plain loop prints it)
+            if st["stop"]:
+                print(STOP_MESSAGES[st["stop"]].format(minfunc=p['kw']['minfunc'], minstep=p['kw']['minstep']))
+            else:
+                print('Stopping search: maximum iterations reached --> {:}'.format(self.key.maxiter))
+            f._finish(x, fx)
+            if k in polished:
+                if scale is not False:
+                    f.generate_result(scale)      # (from the refined parameters: the batch's launch used the swarm's)
+            elif results is not None:
+                r = results[k]
+                f._store_result(f.data.w if r["w"] is None else r["w"], r["real"], r["imag"],
+                                (r["V"], r["I"], r["u"], r["v"]), (r["data_V"], r["data_I"]), call_shift_phase=False)
+
+    def collect(self, call):
+        """Read back and store in one go."""
+        self.store(call, *self.read(call))
+
+
+class _Pipeline:
+    """The three stages of _fit_many_local and what is in flight between them: one thread prepares the batches of a
+    span (error weights, plans, device state), RUN_AT_ONCE threads run batches, one thread reads back and stores."""
+
+    def __init__(self, call, fits):
+        self.call, self.fits, self.plans = call, fits, {}
+        self.host, self.post, self.runner = (ThreadPoolExecutor(max_workers=k) for k in (1, 1, RUN_AT_ONCE))
+        self.pending = None                     # future of the preparation under way
+        self.made = []                          # every batch created and run, or about to (closed by its read, or on an error)
+        self.inflight = collections.deque()     # (future of a batch's run, the batch), in job order
+        self.posted = []                        # futures of the stores
+        self.batched = set()                    # the jobs that went into a batch
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, error, *_):
+        """After an error: let everything under way end, then close every batch made.  Always: end the threads."""
+        if error is not None:
+            waits = [self.pending] if self.pending is not None else []      # (batches made for a span that will not run)
+            waits += [fut for fut, _ in self.inflight] + self.posted        # (runs in flight end before their batches close)
+            for fut in waits:
+                try:
+                    got = fut.result()
+                    if fut is self.pending:
+                        self.made.extend(got[0])
+                except Exception:
+                    pass
+            for b in self.made:
+                b.close()
+        for pool in (self.runner, self.post, self.host):
+            pool.shutdown(wait=True)
+
+    def group(self, members):
+        """Device batches of the members (index, key) that have a partner, ready to run; the others as (index, key)."""
+        groups = {}
+        for i, key in members:
+            groups.setdefault(key, []).append(i)
+        ready, single = [], []
+        for key, idx in groups.items():
+            if key is not None and len(idx) > 1:
+                try:
+                    ready.append(_Batch.create([self.fits[i] for i in idx], [self.plans[i] for i in idx], key, idx))
+                    continue
+                except _cabi.NmrfitError:
+                    # the device refused this batch (LDS budget of its peak counts, memory): its fits run one by one
+                    key = None
+            single.extend((i, key) for i in idx)
+        return ready, single
+
+    def prepare(self, span):
+        """Start the preparation of a span's jobs on the preparing thread (``None``: no further span)."""
+        def work():
+            for i in span:
+                self.plans[i] = self.fits[i]._plan(device_weights=self.call.device_weights)
+            return self.group([(i, self.fits[i]._batch_key(self.plans[i])) for i in span])
+        self.pending = self.host.submit(work) if span is not None else None
+
+    def drain(self, limit):
+        """Wait for the oldest runs until at most ``limit`` are in flight; each batch that has run goes to the thread
+        that reads back and stores, in job order (pyswarm's closing lines print in job order)."""
+        while len(self.inflight) > limit:
+            fut, b = self.inflight.popleft()
+            fut.result()
+            self.posted.append(self.post.submit(b.collect, self.call))
+
+    def run(self, ready, last=False):
+        self.made.extend(ready)
+        for n, b in enumerate(ready):
+            self.batched.update(b.idx)
+            if last and n == len(ready) - 1 and not self.posted and not self.inflight:
+                # the only batch of the call: nothing to overlap it with -- run and read back here, without a thread's
+                # first HIP call in the way (a 40-job list is 30 ms in all)
+                b.run()
+                b.collect(self.call)
+                continue
+            # RUN_AT_ONCE batches are driven at the same time (threads of their own: the C calls release the GIL): while
+            # the last swarms of one batch finish -- a generation of three swarms costs a launch of 8-20 us whatever it
+            # holds -- or its results travel to the host, the other batch fills the device
+            self.drain(RUN_AT_ONCE - 1)
+            self.inflight.append((self.runner.submit(b.run), b))
+
+    def finish(self):
+        self.drain(0)
+        for p in self.posted:
+            p.result()
+
+
+def _fit_many_local(jobs, call):
     fits = []
     for job in jobs:
-        args = dict(kwargs, **job)
+        args = dict(call.kwargs, **job)
         fits.append(utils.FitUtility(args.pop("data"), args.pop("lower"), args.pop("upper"), **args))
-    plans = {}
-    alone = list(range(len(fits)))
-    if batch and len(fits) > 1:
-        n = len(fits)
-        nspans = -(-n // _batch_jobs(n))
-        size = -(-n // nspans)
-        spans = [range(a, min(a + size, n)) for a in range(0, n, size)]
+    if not (call.batch and len(fits) > 1):
+        return _fit_alone(fits, {}, range(len(fits)), call)
+    n = len(fits)
+    size = -(-n // -(-n // _batch_jobs(n)))      # spans of equal size, as many as batches of _batch_jobs(n) need
+    spans = [range(a, min(a + size, n)) for a in range(0, n, size)]
+    leftover = []
+    with _Pipeline(call, fits) as pipe:      # (on an error it waits for what is under way and closes every batch made)
+        pipe.prepare(spans[0])
+        for c in range(len(spans)):
+            ready, single = pipe.pending.result()
+            pipe.prepare(spans[c + 1] if c + 1 < len(spans) else None)
+            leftover.extend(single)
+            pipe.run(ready, last=(c + 1 == len(spans) and not any(key is not None for _, key in leftover)))
+        # what found no partner inside its span may have one in another
+        ready, _ = pipe.group([(i, key) for i, key in leftover if key is not None])
+        pipe.run(ready, last=True)
+        pipe.finish()
+    return _fit_alone(fits, pipe.plans, [i for i in range(n) if i not in pipe.batched], call)
 
-        def group(members):
-            """Device batches of the members that have a partner, ready to run; the others as (index, key)."""
-            groups = {}
-            for i, key in members:
-                groups.setdefault(key, []).append(i)
-            ready, single = [], []
-            for key, idx in groups.items():
-                if key is not None and len(idx) > 1:
-                    try:
-                        ready.append(_batch_create([fits[i] for i in idx], [plans[i] for i in idx], key) + (idx,))
-                        continue
-                    except NmrfitError:
-                        # the device refused this batch (LDS budget of its peak counts, memory): its fits run one by one
-                        key = None
-                single.extend((i, key) for i in idx)
-            return ready, single
 
-        def prepare(span):
-            for i in span:
-                plans[i] = fits[i]._plan(device_weights=bool(device_weights))
-            return group([(i, fits[i]._batch_key(plans[i])) for i in span])
-
-        leftover = []
-        batched = set()
-        made = []          # every batch created and not yet closed (closed by _batch_collect, or below on an error)
-        import collections
-        with ThreadPoolExecutor(max_workers=1) as host, ThreadPoolExecutor(max_workers=1) as post, \
-                ThreadPoolExecutor(max_workers=RUN_AT_ONCE) as runner:
-            pending = host.submit(prepare, spans[0])
-            posted = []
-            inflight = collections.deque()      # (future of a batch's run, the batch), in job order
-            try:
-                def drain(limit):
-                    """Wait for the oldest runs until at most ``limit`` are in flight; what each read back goes to the
-                    thread that stores results, in job order (pyswarm's closing lines print in job order)."""
-                    while len(inflight) > limit:
-                        fut, (fb, bfits, bplans, key, _) = inflight.popleft()
-                        got = fut.result()
-                        if got is None:
-                            posted.append(post.submit(_batch_collect, fb, bfits, bplans, key, scale, threads, **bp))
-                        else:
-                            posted.append(post.submit(_batch_store, bfits, bplans, key, got[0], got[1], got[2], scale, threads))
-
-                def run_and_read(fb, bfits, key):
-                    fb.run(key[4], key[5])                      # (maxiter, check_every)
-                    if not READ_ON_RUNNER:
-                        return None
-                    return _batch_read(fb, bfits, scale, **bp)  # status, best rows, reconstruction; closes the batch
-
-                def run(ready, last=False):
-                    made.extend(r[0] for r in ready)
-                    for n, b in enumerate(ready):
-                        fb, bfits, bplans, key, idx = b
-                        batched.update(idx)
-                        if last and n == len(ready) - 1 and not posted and not inflight:
-                            # the only batch of the call: nothing to overlap it with -- run and read back here, without
-                            # a thread's first HIP call in the way (a 40-job list is 30 ms in all)
-                            fb.run(key[4], key[5])
-                            _batch_collect(fb, bfits, bplans, key, scale, threads, **bp)
-                            continue
-                        # RUN_AT_ONCE batches are driven at the same time (threads of their own: the C calls release
-                        # the GIL): while the last swarms of one batch finish -- a generation of three swarms costs a
-                        # launch of 8-20 us whatever it holds -- or its results travel to the host, the other batch
-                        # fills the device
-                        drain(RUN_AT_ONCE - 1)
-                        inflight.append((runner.submit(run_and_read, fb, bfits, key), b))
-                for c in range(len(spans)):
-                    ready, single = pending.result()
-                    pending = host.submit(prepare, spans[c + 1]) if c + 1 < len(spans) else None
-                    leftover.extend(single)
-                    run(ready, last=(c + 1 == len(spans) and not any(key is not None for _, key in leftover)))
-                # what found no partner inside its span may have one in another
-                ready, _ = group([(i, key) for i, key in leftover if key is not None])
-                run(ready, last=True)
-                drain(0)
-                for p in posted:
-                    p.result()
-            except BaseException:
-                if pending is not None:      # (batches made for a span that will not run)
-                    try:
-                        made.extend(r[0] for r in pending.result()[0])
-                    except Exception:
-                        pass
-                for fut, _ in inflight:      # (runs in flight: let them end before their batches are closed)
-                    try:
-                        fut.result()
-                    except Exception:
-                        pass
-                for p in posted:
-                    try:
-                        p.result()
-                    except Exception:
-                        pass
-                for fb in made:
-                    fb.close()
-                raise
-        alone = [i for i in range(len(fits)) if i not in batched]
-    if not alone:
-        return fits
-
+def _fit_alone(fits, plans, alone, call):
+    """The fits that ran in no batch, through fit() -- with the plan made for them, if any -- on ``call.threads``
+    threads; serially when any carries an ``exchange`` (a communicator serves one swarm at a time)."""
     def lone(i):
         fits[i].fit(plan=plans.get(i))
-        if scale is not False:
-            fits[i].generate_result(scale)
-    with_exchange = any(fits[i].options.get("exchange") is not None for i in alone)
-    if threads <= 1 or len(alone) <= 1 or with_exchange:
+        if call.scale is not False:
+            fits[i].generate_result(call.scale)
+    if call.threads <= 1 or len(alone) <= 1 or any(fits[i].options.get("exchange") is not None for i in alone):
         for i in alone:
             lone(i)
-        return fits
-    with ThreadPoolExecutor(max_workers=int(threads)) as pool:
-        list(pool.map(lone, alone))
-    return fits
-
-
-def _batch_create(fits, plans, key):
-    """The device state of one batch (spectra, weights, boxes, swarms) -- everything up to the first launch."""
-    from .batch import FitBatch
-    device, _, _, variant, _, _, fit_im = key
-    swarmsize = [int(p['swarmsize']) for p in plans]
-    # (all or nothing: the plans of one fit_many call either all carry their regions -- device_weights -- or none does)
-    regions = [p['regions'] for p in plans] if all('regions' in p for p in plans) else None
-    if regions is None:
-        spectra = [(f.data.w, f.data.u, f.data.v, f.weights) for f in fits]
     else:
-        spectra = [(f.data.w, f.data.u, f.data.v) for f in fits]
-    kw = {name: [p['kw'][name] for p in plans] for name in ("omega", "phip", "phig", "minstep", "minfunc")}
-    fb = FitBatch(spectra, [f.lower for f in fits], [f.upper for f in fits], swarmsize=swarmsize,
-                  seeds=[p['seed'] for p in plans], variant=variant, fit_im=fit_im, device=device, regions=regions, **kw)
-    return fb, fits, plans, key
-
-
-def _fit_batch(fits, plans, key, generate=False):
-    """One device batch: FitBatch over the fits' spectra, run to the common maxiter, results into the FitUtility objects
-    (what FitUtility.fit does for one, utils.py:164-189; with ``generate`` also what generate_result does)."""
-    fb, fits, plans, key = _batch_create(fits, plans, key)
-    try:
-        fb.run(key[4], key[5])
-    except BaseException:
-        fb.close()
-        raise
-    _batch_collect(fb, fits, plans, key, 1 if generate is True else generate)
-
-
-def _lsq_max_d():
-    from . import _cabi
-    return _cabi.LSQ_MAX_D
-
-
-def _batch_read(fb, fits, scale=False, batch_polish=False):
-    """What is read from the device after a batch's generations: stop codes, best positions and -- ``scale`` not False --
-    the reconstruction of every fit in one launch (FitBatch.generate).  ``batch_polish``: the fits with
-    options['polish'] and fit_im=False are refined here, in lock step, from the batch's resident spectra
-    (FitBatch.polish); their entries of ``best`` are then the refined ones and _batch_store leaves them alone.
-    Closes the batch."""
-    polished = sum(1 for f in fits if f.options.get('polish', False))
-    with fb:
-        status = fb.status()
-        best = fb.best()
-        results = fb.generate(scale) if scale is not False and polished < len(fits) else None
-        if batch_polish:
-            which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and not f.fit_im]
-            # (the launch covers the whole batch: one fit beyond the kernel's D leaves all of them to the per-fit path)
-            if which and max(len(f.lower) for f in fits) <= _lsq_max_d():
-                refined = fb.polish([x for x, _ in best], which=which)
-                for k in which:
-                    best[k] = refined[k]
-                    fits[k]._batch_polished = True
-    return status, best, results
-
-
-def _batch_collect(fb, fits, plans, key, scale=False, threads=1, batch_polish=False):
-    """Read back (``_batch_read``) and store (``_batch_store``) in one go."""
-    status, best, results = _batch_read(fb, fits, scale, **({"batch_polish": True} if batch_polish else {}))
-    _batch_store(fits, plans, key, status, best, results, scale, threads)
-
-
-def _batch_store(fits, plans, key, status, best, results, scale=False, threads=1):
-    """A batch's results into the FitUtility objects (what FitUtility.fit and generate_result leave behind).  Fits with
-    options['polish'] are refined first (FitUtility._polish, ``threads`` at a time) and reconstructed from the refined
-    parameters."""
-    from .pso import STOP_MESSAGES
-    maxiter = key[4]
-    polished = [k for k, f in enumerate(fits) if f.options.get('polish', False)]
-    # (refined already, with the batch still resident: fit_many(batch_polish=True), _batch_read)
-    per_fit = [k for k in polished if not getattr(fits[k], "_batch_polished", False)]
-    if per_fit:
-        def refine(k):
-            return fits[k]._polish(best[k][0], best[k][1], plans[k])
-        if threads > 1 and len(per_fit) > 1:
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=int(threads)) as pool:
-                refined = list(pool.map(refine, per_fit))
-        else:
-            refined = [refine(k) for k in per_fit]
-        for k, xf in zip(per_fit, refined):
-            best[k] = xf
-    for k, (f, p, st, (x, fx)) in enumerate(zip(fits, plans, status, best)):
-        # (pyswarm's closing line, once per fit like the plain loop prints it)
-        if st["stop"]:
-            print(STOP_MESSAGES[st["stop"]].format(minfunc=p['kw']['minfunc'], minstep=p['kw']['minstep']))
-        else:
-            print('Stopping search: maximum iterations reached --> {:}'.format(maxiter))
-        f._finish(x, fx)
-        if k in polished:
-            if scale is not False:
-                f.generate_result(scale)      # (from the refined parameters: the batch's launch used the swarm's)
-        elif results is not None:
-            r = results[k]
-            f._store_result(f.data.w if r["w"] is None else r["w"], r["real"], r["imag"],
-                            (r["V"], r["I"], r["u"], r["v"]), (r["data_V"], r["data_I"]), call_shift_phase=False)
+        with ThreadPoolExecutor(max_workers=int(call.threads)) as pool:
+            list(pool.map(lone, alone))
+    return fits

@@ -23,6 +23,8 @@ multiprocessing.Pool (utils.py:182, 259-261), which the batched launches replace
 ``fit_im=True`` follows the reference to the letter (equations.py:197-209: the imaginary
 model is the last peak's line only); ``fit_im="sum"`` fits the imaginary part of all peaks.
 """
+import typing
+
 import numpy as np
 
 from . import _cabi, equations, proc_autophase, pso
@@ -229,6 +231,15 @@ def small_shard_warning(S_local, N, P, world, rank=0):
     return True
 
 
+class BatchKey(typing.NamedTuple):
+    """What the fits of one device batch have in common (FitUtility._batch_key; core.fit_many groups by it)."""
+    device: int
+    variant: int
+    maxiter: int
+    check_every: int
+    fit_im: int          # (the imaginary-channel mode, equations.fit_im_mode)
+
+
 class FitUtility:
     """Interface used to perform a fit of the data (reference: nmrfit/utils.py:96)."""
 
@@ -323,7 +334,7 @@ class FitUtility:
             return None
         if plan['variant'] not in (_cabi.VARIANT_DEFAULT, _cabi.VARIANT_FARFIELD) or len(self.lower) > 400:
             return None
-        return (self._device(), None, None, plan['variant'], int(plan['maxiter']), int(plan['check_every']), mode)
+        return BatchKey(self._device(), plan['variant'], int(plan['maxiter']), int(plan['check_every']), mode)
 
     def _finish(self, xopt, fopt):
         self.params = xopt

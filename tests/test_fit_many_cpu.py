@@ -40,13 +40,13 @@ def test_batch_key_groups_equal_shapes_only():
     assert key(a, options={"swarmsize": 100}) == ka                  # (round 6: swarm sizes may differ too)
     assert key(a, options={"maxiter": 100}) != ka and key(a, options={"check_every": 8}) != ka
     assert key(a, fit_im=True) not in (None, ka) and key(a, fit_im="sum") not in (None, ka, key(a, fit_im=True))
-    assert key(big, fit_im="sum")[3] == _cabi.VARIANT_FARFIELD         # (every peak's imaginary line on a large grid: the far-field
+    assert key(big, fit_im="sum").variant == _cabi.VARIANT_FARFIELD    # (every peak's imaginary line on a large grid: the far-field
                                                                        # kernel, batched too since round 6)
-    assert key(_job(8192, 6, 5), fit_im="sum")[3] == _cabi.VARIANT_DEFAULT
+    assert key(_job(8192, 6, 5), fit_im="sum").variant == _cabi.VARIANT_DEFAULT
     assert key(a, options={"polish": True}) == ka                     # (round 6: the swarm of a polished fit runs in the batch)
     assert key(a, options={"exchange": object()}) is None
     assert key(a, options={"variant": "norec"}) is None
-    assert key(big)[3] == _cabi.VARIANT_FARFIELD and key(a)[3] == _cabi.VARIANT_DEFAULT
+    assert key(big).variant == _cabi.VARIANT_FARFIELD and key(a).variant == _cabi.VARIANT_DEFAULT
 
 
 def test_jobs_with_a_communicator_run_one_after_another(monkeypatch):
@@ -88,26 +88,23 @@ def _fake_pipeline(monkeypatch, refuse=()):
     """core's device calls replaced: returns the logs (made, ran, collected, lone, batches)."""
     made, ran, collected, lone, batches = [], [], [], [], []
 
-    def fake_create(fits, plans, key):
+    def fake_create(fits, plans, key, idx):
         tags = [f.options["tag"] for f in fits]
         if any(t in refuse for t in tags):
             raise _cabi.NmrfitError(_cabi.E_UNSUPPORTED, "too many peaks for the kernel's LDS records in a batched launch")
         made.append((threading.get_ident(), tags))
         batches.append(_FakeBatch(ran, tags))
-        return batches[-1], fits, plans, key
+        return core._Batch(batches[-1], fits, plans, key, idx)
 
-    def fake_read(fb, fits, scale=False):
-        fb.close()
-        return [fb.tags, threading.get_ident()], None, scale
+    def fake_read(self, call):
+        self.fb.close()
+        return set(), [self.fb.tags, threading.get_ident()], None, call.scale
 
-    def fake_store(fits, plans, key, status, best, results, scale=False, threads=1):
-        collected.append((threading.get_ident(), status[0], scale))
-        assert threads >= 1 and results == scale
-        for f in fits:
+    def fake_store(self, call, refined, status, best, results):
+        collected.append((threading.get_ident(), status[0], call.scale))
+        assert call.threads >= 1 and results == call.scale
+        for f in self.fits:
             f.params, f.error = np.zeros(len(f.lower)), 0.0
-
-    def fake_collect(fb, fits, plans, key, scale=False, threads=1):
-        fake_store(fits, plans, key, *fake_read(fb, fits, scale), scale, threads)
 
     def fake_fit(self, plan=None):
         lone.append((self.options["tag"], plan is not None))
@@ -115,10 +112,9 @@ def _fake_pipeline(monkeypatch, refuse=()):
 
     def fake_generate(self, scale=1):
         self.generated = scale
-    monkeypatch.setattr(core, "_batch_create", fake_create)
-    monkeypatch.setattr(core, "_batch_collect", fake_collect)
-    monkeypatch.setattr(core, "_batch_read", fake_read)
-    monkeypatch.setattr(core, "_batch_store", fake_store)
+    monkeypatch.setattr(core._Batch, "create", staticmethod(fake_create))
+    monkeypatch.setattr(core._Batch, "read", fake_read)
+    monkeypatch.setattr(core._Batch, "store", fake_store)
     monkeypatch.setattr(utils.FitUtility, "fit", fake_fit)
     monkeypatch.setattr(utils.FitUtility, "generate_result", fake_generate)
     return made, ran, collected, lone, batches
@@ -189,13 +185,91 @@ def test_an_error_in_a_run_closes_every_batch(monkeypatch):
     assert all(b.closed for b in batches) and len(batches) >= 2
 
 
+class _ResidentBatch:
+    """Stands in for batch.FitBatch after its generations: status / best / generate / polish / close, every call logged."""
+
+    def __init__(self, fits):
+        self.fits, self.calls = fits, []
+
+    def status(self):
+        return [dict(iteration=7, stop=0, fg=1.0) for _ in self.fits]
+
+    def best(self):
+        return [(np.full(len(f.lower), float(k)), 10.0 + k) for k, f in enumerate(self.fits)]
+
+    def generate(self, scale):
+        self.calls.append(("generate", scale))
+        n = len(self.fits[0].data.w)
+        return [dict(w=None, real=np.full((2, n), 100.0 + k), imag=np.zeros((2, n)), V=np.zeros(n), I=np.zeros(n),
+                     u=np.zeros(n), v=np.zeros(n), data_V=np.zeros(n), data_I=np.zeros(n)) for k in range(len(self.fits))]
+
+    def polish(self, X, which):
+        self.calls.append(("polish", list(which)))
+        return [(x + 0.5, 0.25) if k in which else (x, None) for k, x in enumerate(X)]
+
+    def close(self):
+        self.calls.append(("close",))
+
+
+def test_read_and_store_know_which_fits_the_batch_refined(monkeypatch, capsys):
+    """The real read and store of a device batch (no device: a stand-in holds what is resident).  Fit A asks for the
+    polish, fit B for the polish with fit_im=True, fit C for neither.  With batch_polish the batch refines A alone and
+    store's per-fit _polish is left with B; without it both go through _polish.  A and B are reconstructed from their
+    refined parameters, C takes the batch's launch -- and which fits the batch refined travels from read to store as a
+    value: the fits carry no mark of it."""
+    per_fit, generated = [], []
+
+    def fake_polish(self, xopt, fopt, plan):
+        per_fit.append(self.options["tag"])
+        return xopt - 0.5, 0.5
+
+    def fake_generate(self, scale=1):
+        generated.append((self.options["tag"], scale, np.array(self.params)))
+    monkeypatch.setattr(utils.FitUtility, "_polish", fake_polish)
+    monkeypatch.setattr(utils.FitUtility, "generate_result", fake_generate)
+    for batch_polish in (True, False):
+        per_fit.clear(), generated.clear()
+        jobs = [_job(512, 2, 70, options={"tag": "A", "polish": True}),
+                _job(512, 2, 71, fit_im=True, options={"tag": "B", "polish": True}), _job(512, 2, 72, options={"tag": "C"})]
+        fits = [utils.FitUtility(j.pop("data"), j.pop("lower"), j.pop("upper"), summary=False, **j) for j in jobs]
+        plans = [f._plan() for f in fits]
+        before = [set(vars(f)) for f in fits]
+        fb = _ResidentBatch(fits)
+        b = core._Batch(fb, fits, plans, fits[0]._batch_key(plans[0]), [0, 1, 2])
+        call = core._Call(1, True, {}, 1, False, batch_polish)
+        refined, status, best, results = b.read(call)
+        assert fb.calls[-1] == ("close",) and fb.calls[0] == ("generate", 1)
+        b.store(call, refined, status, best, results)
+        D = len(fits[0].lower)
+        if batch_polish:
+            assert [c for c in fb.calls if c[0] == "polish"] == [("polish", [0])] and refined == {0}
+            assert per_fit == ["B"]
+            np.testing.assert_array_equal(fits[0].params, np.full(D, 0.5))          # the stand-in's refined ones
+            assert fits[0].error == 0.25
+        else:
+            assert not [c for c in fb.calls if c[0] == "polish"] and refined == set()
+            assert per_fit == ["A", "B"]
+            np.testing.assert_array_equal(fits[0].params, np.full(D, -0.5))
+            assert fits[0].error == 0.5
+        np.testing.assert_array_equal(fits[1].params, np.full(D, 0.5))              # (B: 1 - 0.5, FitUtility._polish)
+        np.testing.assert_array_equal(fits[2].params, np.full(D, 2.0))              # (C: the swarm's)
+        assert (fits[1].error, fits[2].error) == (0.5, 12.0)
+        assert [(tag, scale) for tag, scale, _ in generated] == [("A", 1), ("B", 1)]
+        np.testing.assert_array_equal(generated[0][2], fits[0].params)              # reconstructed from the refined parameters
+        assert np.all(np.stack(fits[2].real_contribs) == 102.0) and not hasattr(fits[0], "real_contribs")   # C: the batch's launch
+        assert capsys.readouterr().out.count("Stopping search: maximum iterations reached --> 2000") == 3
+        for f, had in zip(fits, before):
+            assert not [name for name in vars(f) if "polished" in name]      # (no mark of the batch's polish on the fit)
+            assert set(vars(f)) - had <= {"params", "error", "u", "v", "V", "I", "w", "real_contribs", "imag_contribs"}
+
+
 def test_the_rank_device_reaches_jobs_that_bring_their_own_options(monkeypatch):
     """a job's own `options` replaces the shared dict when the two are merged, so the device of a
     sharded (or devices=[...]) call must be stamped into every job's options -- a seed per job is exactly what callers
     pass."""
     seen = []
 
-    def fake_local(jobs, threads, batch, kwargs, generate=False):
+    def fake_local(jobs, call):
         seen.append([dict(j.get("options") or {}) for j in jobs])
         out = []
         for j in jobs:
@@ -218,11 +292,13 @@ def test_the_rank_device_reaches_jobs_that_bring_their_own_options(monkeypatch):
     monkeypatch.setenv("LOCAL_RANK", "3")
     monkeypatch.setenv("RANK", "0")
     monkeypatch.setenv("WORLD_SIZE", "1")
-    core._fit_many_sharded(jobs, 1, True, dict(summary=False, options={"maxiter": 5}), 0, 1, channel=Chan())
+    core._fit_many_sharded(jobs, core._Call(1, True, dict(summary=False, options={"maxiter": 5}), False, False, False), 0, 1,
+                            channel=Chan())
     assert [o["device"] for o in seen[-1]] == [3] * 5
     assert [o.get("seed") for o in seen[-1]] == [0, 1, 2, 3, None] and all(o["maxiter"] == 5 for o in seen[-1])
     # a device the job names itself wins in the sharded mode ...
-    core._fit_many_sharded([_job(512, 2, 1, options={"device": 6})], 1, True, dict(summary=False), 0, 1, channel=Chan())
+    core._fit_many_sharded([_job(512, 2, 1, options={"device": 6})], core._Call(1, True, dict(summary=False), False, False, False),
+                            0, 1, channel=Chan())
     assert seen[-1][0]["device"] == 6
     # ... and devices=[...] assigns -- without a TypeError when the job's options already hold a device
     seen.clear()
@@ -275,7 +351,7 @@ def local(my_jobs):          # stands in for the GPU: a result that names the jo
         out.append(f)
     return out
 
-res = core._fit_many_sharded(jobs, 1, True, dict(summary=False), rank, world, local=local)
+res = core._fit_many_sharded(jobs, core._Call(1, True, dict(summary=False), False, False, False), rank, world, local=local)
 print(json.dumps(dict(rank=rank, owners=[int(round(r.params[0] - j["lower"][0])) for r, j in zip(res, jobs)],
                       errors=[r.error for r in res], seeds=[r.seed for r in res])))
 """

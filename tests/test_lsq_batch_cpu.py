@@ -193,15 +193,16 @@ def test_null_arguments_are_refused_without_a_gpu():
 
 
 def test_batch_polish_is_fit_manys_own_argument(monkeypatch):
-    """The flag reaches the batch read-back and nothing else; without it the calls are today's."""
+    """The flag reaches the batch read-back in fit_many's call record and nothing else; without it the record is the
+    plain call's."""
     from nmrfit_amd import core
     got = []
 
-    def fake_local(jobs, threads, batch, kwargs, generate=False, **flags):
-        got.append(flags)
+    def fake_local(jobs, call):
+        got.append((call.device_weights, call.batch_polish))
         return []
     monkeypatch.setattr(core, "_fit_many_local", fake_local)
     core.fit_many([], batch_polish=True)
     core.fit_many([])
     core.fit_many([], device_weights=True, batch_polish=True)
-    assert got == [{"batch_polish": True}, {}, {"device_weights": True, "batch_polish": True}]
+    assert got == [(False, True), (False, False), (True, True)]

@@ -21,8 +21,8 @@ def wrap(obj, name, tag):
         log.append((tag, threading.current_thread().name[-8:], (ts - t0[0]) * 1e3, (time.perf_counter() - t0[0]) * 1e3))
         return r
     setattr(obj, name, g)
-wrap(core, "_batch_create", "create")
-wrap(core, "_batch_collect", "collect")
+wrap(core._Batch, "create", "create")
+wrap(core._Batch, "collect", "collect")
 wrap(batch.FitBatch, "run", "run")
 wrap(batch.FitBatch, "generate", "  generate")
 wrap(batch.FitBatch, "close", "  close")
