@@ -163,6 +163,13 @@ LSQ_SIGNATURES = {
     "nmrfit_jacobian": [_VP, _I32, _VP, _VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_batch_normal_equations": [_VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# LSQ_IM_SIGNATURES: include/nmrfit_amd_lsq_im.h (the same on both channels of a fit_im fit: imaginary residual rows, the
+# Jacobian and the normal equations per channel)
+LSQ_IM_SIGNATURES = {
+    "nmrfit_residual_batch_im": [_VP, _I64, _I32, _VP, _INT, _VP, _VP],
+    "nmrfit_jacobian_im": [_VP, _I32, _VP, _VP, ctypes.c_double, _INT, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_normal_equations_im": [_VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                    # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -266,7 +273,8 @@ def lib():
         # HIP call this library makes.  A value the user exported wins.
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
-        for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()):
+        for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
+                + list(LSQ_IM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -184,13 +184,20 @@ class FitBatch:
         return out
 
     # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
-    def normal_equations(self, X):
+    def normal_equations(self, X, channels="real"):
         """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``
         would make for each fit's box, their residual rows for ALL fits in one launch over the batch's resident spectra,
         A = J^T J and g = J^T r reduced on the device (csrc/lsq.hip), f the launch's own objective value at X[k].
         Bit-identical to ``lsq.ResidualModel(Evaluator(spectrum), lower, upper).normal_equations(X[k])`` fit by fit, in
-        any batch.  The swarms are not touched.  D <= 76 for every fit."""
+        any batch.  The swarms are not touched.  D <= 76 for every fit.
+
+        ``channels="both"`` (a batch created with a ``fit_im`` mode; nmrfit_batch_normal_equations_im): the rows of both
+        channels in the same launch, A and g per channel, and per fit the combined ``(H, grad f, f)`` of the objective
+        f = (rho_re + rho_im)/2 the batch's swarms minimise (``lsq.combine_channels``) -- bit-identical to
+        ``lsq.ResidualModel(Evaluator(spectrum), lower, upper, fit_im=mode).normal_equations(X[k])``."""
         from . import lsq
+        if channels not in ("real", "both"):
+            raise ValueError('FitBatch.normal_equations: channels is "real" or "both"')
         if len(X) != self.K:
             raise ValueError("FitBatch.normal_equations: one parameter vector per fit")
         rows, cs = [], []
@@ -207,17 +214,31 @@ class FitBatch:
         aoff = np.concatenate(([0], np.cumsum(D * D)))
         A = np.empty(int(aoff[-1]))
         g = np.empty(int(self.offsets[-1]))
+        if channels == "both":
+            A2, g2, f2 = np.empty(2 * int(aoff[-1])), np.empty(2 * int(self.offsets[-1])), np.empty(2 * self.K)
+            _cabi.check(self._lib.nmrfit_batch_normal_equations_im(self._h, _cabi.ptr(rows), _cabi.ptr(cs), _cabi.ptr(s),
+                                                                   _cabi.ptr(A2), _cabi.ptr(g2), _cabi.ptr(f2)))
+            out = []
+            for k in range(self.K):
+                d = self.D[k]
+                Ak = A2[2 * aoff[k]:2 * aoff[k + 1]].reshape(2, d, d)
+                gk = g2[2 * self.offsets[k]:2 * self.offsets[k + 1]].reshape(2, d)
+                out.append(lsq.combine_channels([(Ak[ch], gk[ch], f2[2 * k + ch]) for ch in (0, 1)]))
+            return out
         f = np.empty(self.K)
         _cabi.check(self._lib.nmrfit_batch_normal_equations(self._h, _cabi.ptr(rows), _cabi.ptr(cs), _cabi.ptr(s), _cabi.ptr(A),
                                                             _cabi.ptr(g), _cabi.ptr(f)))
         return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), g[self.offsets[k]:self.offsets[k + 1]], float(f[k]))
                 for k in range(self.K)]
 
-    def polish(self, X=None, which=None, **kwargs):
+    def polish(self, X=None, which=None, channels="real", **kwargs):
         """Least-squares refinement of the K fits in lock step (``lsq.lm_polish`` over ``normal_equations``): every
         launch evaluates the trial points of all fits still moving.  ``X`` None: from ``best()``.  ``which``: the fits
         to refine (default all); the others come back as they are.  Real-part objective only (fit_im=False batches).
-        Returns per fit ``(x, f)``, f the rows launch's objective value at x -- never above the start's."""
+        Returns per fit ``(x, f)``, f the rows launch's objective value at x -- never above the start's.
+
+        ``channels="both"`` (a batch created with a ``fit_im`` mode): the same loop over the combined normal equations
+        of both channels -- it minimises the objective the batch's swarms minimised, f = (rho_re + rho_im)/2."""
         from . import lsq
         start = self.best()
         if X is None:
@@ -234,7 +255,7 @@ class FitBatch:
             for k, x in zip(which, trial):
                 if x is not None:
                     full[k] = x
-            got = self.normal_equations(full)
+            got = self.normal_equations(full, channels=channels)
             return [None if x is None else got[k] for k, x in zip(which, trial)]
         Xw, fw, info = lsq.lm_polish(provider, [X[k] for k in which], [self.lowers[k] for k in which],
                                      [self.uppers[k] for k in which], **kwargs)

@@ -86,10 +86,17 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       iterations per fit.  Same objective, same start, another solver: ``params`` agree with the per-fit path to the
       minimum's accuracy, not bit for bit; ``error`` is the rows launch's value at the accepted point and never above the
       swarm's; ``generate`` reconstructs from the refined parameters.  Jobs with ``fit_im``, jobs that fell back to lone
-      fits and lone ``fit()`` keep the per-fit path."""
+      fits and lone ``fit()`` keep the per-fit path.
+    * ``batch_polish="both"``: as ``True``, and the jobs with ``options['polish']`` of a ``fit_im`` batch (True or "sum")
+      are refined in lock step too, on BOTH channels (``FitBatch.polish(channels="both")``; csrc/objective_rows_im.hip,
+      include/nmrfit_amd_lsq_im.h): the loop minimises the objective their swarms minimised, (rho_re + rho_im)/2, where
+      the per-fit path refines the real channel and can only accept or reject against it.  ``error`` is that objective
+      at the accepted point, never above the swarm's.  ``fit_im=False`` jobs behave as under ``True``; fits that end
+      up alone and batches with any D > 76 keep the per-fit path."""
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
-    call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights), bool(batch_polish))
+    call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights),
+                 "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish))
     if devices is not None:
         if shard:
             raise ValueError("fit_many: shard=True divides the jobs over PROCESSES, devices=[...] over the GPUs of this "
@@ -117,7 +124,7 @@ class _Call(typing.NamedTuple):
     kwargs: dict                 # fit's keyword arguments, shared by the jobs
     scale: object                # ``generate``: False (no reconstruction), or generate_result's scale (True -> 1)
     device_weights: bool
-    batch_polish: bool
+    batch_polish: object         # False, True (fit_im=False jobs), or "both" (the jobs of fit_im batches too, on both channels)
 
 
 def _result_record(f):
@@ -269,10 +276,13 @@ class _Batch:
             best = fb.best()
             results = fb.generate(call.scale) if call.scale is not False and polished < len(fits) else None
             if call.batch_polish:
-                which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and not f.fit_im]
+                # (a batch has one fit_im mode: with one, its fits are refined here only under "both", on both channels)
+                both = call.batch_polish == "both"
+                which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and (both or not f.fit_im)]
+                kw = dict(channels="both") if any(fits[k].fit_im for k in which) else {}
                 # (the launch covers the whole batch: one fit beyond the kernel's D leaves all of them to the per-fit path)
                 if which and max(len(f.lower) for f in fits) <= _cabi.LSQ_MAX_D:
-                    new = fb.polish([x for x, _ in best], which=which)
+                    new = fb.polish([x for x, _ in best], which=which, **kw)
                     for k in which:
                         best[k] = new[k]
                     refined = set(which)

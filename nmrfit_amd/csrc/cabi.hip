@@ -718,6 +718,120 @@ int nmrfit_jacobian(nmrfit_ctx *ctx, int32_t P, const double *rows, const double
     return NMRFIT_OK;
 }
 
+// include/nmrfit_amd_lsq_im.h: the same on both channels.  The rows launch writes the imaginary rows into a second plane
+// of the same buffer and the two RMSEs of every row; a (fit, channel) pair is then one job of the kernels of lsq.hip.
+static int check_rows_im(int fit_im, const char *who)
+{
+    if (fit_im != NMRFIT_FIT_IM_REFERENCE && fit_im != NMRFIT_FIT_IM_SUM) {
+        set_error(std::string(who) + ": fit_im must be 1 (reference fit_im=True) or 2 (all-peak imaginary model)");
+        return NMRFIT_E_INVALID;
+    }
+    return NMRFIT_OK;
+}
+
+int nmrfit_residual_batch_im(nmrfit_ctx *ctx, int64_t B, int32_t P, const double *X, int fit_im, double *R_out, double *f2_out)
+{
+    int rc = bind(ctx);
+    if (rc != NMRFIT_OK) return rc;
+    if ((rc = check_rows_im(fit_im, "nmrfit_residual_batch_im")) != NMRFIT_OK) return rc;
+    rc = check_batch(ctx, B, P, X, R_out);
+    if (rc != NMRFIT_OK) return rc;
+    if (B == 0) return NMRFIT_OK;
+    const int64_t D = 4 + 3 * (int64_t)P, N = ctx->N;
+    if ((rc = ensure(ctx, &ctx->d_X, &ctx->cap_X, B * D)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_f, &ctx->cap_f, 2 * B)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_R, &ctx->cap_R, 2 * B * N)) != NMRFIT_OK) return rc;
+    NMRFIT_HIP(hipMemcpyAsync(ctx->d_X, X, (size_t)(B * D) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_objective(ctx, B, P, ctx->d_X, ctx->d_f, ctx->d_R, nullptr, nullptr, fit_im)) != NMRFIT_OK) return rc;
+    NMRFIT_HIP(hipMemcpyAsync(R_out, ctx->d_R, (size_t)(2 * B * N) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (f2_out)
+        NMRFIT_HIP(hipMemcpyAsync(f2_out, ctx->d_f, (size_t)(2 * B) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NMRFIT_HIP(hipStreamSynchronize(ctx->stream));
+    return NMRFIT_OK;
+}
+
+int nmrfit_jacobian_im(nmrfit_ctx *ctx, int32_t P, const double *rows, const double *c, double s, int fit_im, double *J_out,
+                       double *r_out, double *A_out, double *g_out, double *f2_out)
+{
+    int rc = bind(ctx);
+    if (rc != NMRFIT_OK) return rc;
+    if (!rows || !c) {
+        set_error("nmrfit_jacobian_im: null rows or c");
+        return NMRFIT_E_INVALID;
+    }
+    if ((rc = check_rows_im(fit_im, "nmrfit_jacobian_im")) != NMRFIT_OK) return rc;
+    rc = check_batch(ctx, 1, P, rows, c);
+    if (rc != NMRFIT_OK) return rc;
+    const int64_t D = 4 + 3 * (int64_t)P, B = D + 1, N = ctx->N;
+    const bool sums = A_out || g_out;
+    if (sums && D > kLsqMaxD) {
+        set_error("nmrfit_jacobian_im: A and g need D = 4 + 3 P <= " + std::to_string(kLsqMaxD));
+        return NMRFIT_E_UNSUPPORTED;
+    }
+    if (!J_out && !r_out && !sums && !f2_out) return NMRFIT_OK;
+    constexpr int64_t kJobDoubles = (sizeof(LsqJob) + sizeof(double) - 1) / sizeof(double);
+    static_assert(sizeof(LsqJob) % sizeof(double) == 0, "two jobs follow each other in a buffer of doubles");
+    LsqJob job[2] = {};
+    lsq_segments(N, &job[0].nseg, &job[0].seg_tiles);
+    const int64_t n_partial = sums ? job[0].nseg * lsq_sums(D) : 0;
+    const int64_t n_J = J_out ? N * D : 0, n_r = r_out ? N : 0, n_Ag = sums ? D * D + D : 0;
+    const int64_t n_ch = n_J + n_r + n_partial + n_Ag;   // one channel's share of the workspace
+    if ((rc = ensure(ctx, &ctx->d_X, &ctx->cap_X, B * D + D + 2 * kJobDoubles)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_f, &ctx->cap_f, 2 * B)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_R, &ctx->cap_R, 2 * B * N)) != NMRFIT_OK) return rc;
+    if ((rc = ensure(ctx, &ctx->d_lsq, &ctx->cap_lsq, 2 * n_ch + 1)) != NMRFIT_OK) return rc;
+    double *d_c = ctx->d_X + B * D, *d_job = d_c + D;
+    double *d_J[2], *d_r[2], *d_A[2], *d_g[2];
+    for (int ch = 0; ch < 2; ++ch) {
+        d_J[ch] = ctx->d_lsq + ch * n_ch;
+        d_r[ch] = d_J[ch] + n_J;
+        double *d_partial = d_r[ch] + n_r;
+        d_A[ch] = d_partial + n_partial;
+        d_g[ch] = d_A[ch] + (sums ? D * D : 0);
+        LsqJob &q = job[ch];
+        q.R = ctx->d_R + ch * B * N;   // the channel's plane of the rows
+        q.c = d_c;
+        q.s = s;
+        q.N = N;
+        q.D = (int32_t)D;
+        q.nseg = job[0].nseg;
+        q.seg_tiles = job[0].seg_tiles;
+        q.J = J_out ? d_J[ch] : nullptr;
+        q.r = r_out ? d_r[ch] : nullptr;
+        q.partial = sums ? d_partial : nullptr;
+        q.A = sums ? d_A[ch] : nullptr;
+        q.g = sums ? d_g[ch] : nullptr;
+    }
+    hipStream_t st = ctx->stream;
+    std::vector<double> up((size_t)(B * D + D + 2 * kJobDoubles));
+    memcpy(up.data(), rows, (size_t)(B * D) * sizeof(double));
+    memcpy(up.data() + B * D, c, (size_t)D * sizeof(double));
+    memcpy(up.data() + B * D + D, job, sizeof job);
+    // (pageable host memory: the copy has left `up` when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(ctx->d_X, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = launch_objective(ctx, B, P, ctx->d_X, ctx->d_f, ctx->d_R, nullptr, nullptr, fit_im)) != NMRFIT_OK) return rc;
+    if (J_out || r_out || sums) {
+        if (D <= kLsqMaxD) {
+            rc = launch_lsq(st, reinterpret_cast<const LsqJob *>(d_job), 2, (int32_t)D, sums);
+        } else {
+            rc = launch_lsq_plain(st, job[0]);
+            if (rc == NMRFIT_OK) rc = launch_lsq_plain(st, job[1]);
+        }
+        if (rc != NMRFIT_OK) return rc;
+    }
+    for (int ch = 0; ch < 2; ++ch) {
+        if (A_out) NMRFIT_HIP(hipMemcpyAsync(A_out + ch * D * D, d_A[ch], (size_t)(D * D) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (g_out) NMRFIT_HIP(hipMemcpyAsync(g_out + ch * D, d_g[ch], (size_t)D * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (f2_out) NMRFIT_HIP(hipMemcpyAsync(f2_out, ctx->d_f, 2 * sizeof(double), hipMemcpyDeviceToHost, st));   // row 0's pair
+    for (int ch = 0; ch < 2; ++ch) {
+        if (r_out && (rc = staged_d2h(ctx->device, st, r_out + ch * N, d_r[ch], (size_t)N * sizeof(double))) != NMRFIT_OK) return rc;
+        if (J_out && (rc = staged_d2h(ctx->device, st, J_out + ch * N * D, d_J[ch], (size_t)(N * D) * sizeof(double))) != NMRFIT_OK) return rc;
+    }
+    NMRFIT_HIP(hipStreamSynchronize(st));
+    return NMRFIT_OK;
+}
+
 int nmrfit_dev_alloc(nmrfit_ctx *ctx, int64_t bytes, void **dptr)
 {
     int rc = bind(ctx);

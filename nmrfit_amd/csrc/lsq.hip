@@ -141,7 +141,10 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_jacobian_plain_kernel(LsqJob 
 // one segment (the wave walks the fit's whole grid and writes f itself, block sums in grid order).  The body is the lone
 // residual kernel's -- objective_body<DEFAULT, WRITE_R> -- on the fit's own block structure, which follows from its N
 // alone: rows and f are what nmrfit_residual_batch gives on a context of the same spectrum, bit for bit.
-__global__ __launch_bounds__(kWave *kWavesPerBlock, objective_min_waves(NMRFIT_VARIANT_DEFAULT, 0)) void residual_rows_batch_kernel(
+// FIT_IM 1, 2 (a batch has one mode): rows of both channels, R [2][S][N] and f [S][2] per fit -- what
+// nmrfit_residual_batch_im gives (include/nmrfit_amd_lsq_im.h).  Instantiation 0 is the kernel as it was.
+template <int FIT_IM>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, objective_min_waves(NMRFIT_VARIANT_DEFAULT, FIT_IM)) void residual_rows_batch_kernel(
     const RowsFit *__restrict__ fits, int blocks_per_fit, const unsigned aux_off)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, objective_min_waves(NMRFIT_V
     if (threadIdx.x == 0) wsums[2 * kMaxBlocks + 1] = 0.0;   // no personal bests here
     const int64_t g = lblock * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const PsoFused none{};
-    objective_body<NMRFIT_VARIANT_DEFAULT, true, 0, kWavesPerBlock>(lds_raw, g, lblock, d.wc, d.u, d.v, d.wt, d.chunk, d.X, d.S, d.P, d.N,
+    objective_body<NMRFIT_VARIANT_DEFAULT, true, FIT_IM, kWavesPerBlock>(lds_raw, g, lblock, d.wc, d.u, d.v, d.wt, d.chunk, d.X, d.S, d.P, d.N,
                                                                    d.w0, d.wspan, 1, d.seg_len, d.blk_chunks, d.n_blocks, d.n_blocks,
                                                                    d.lane_step, d.rec_devk, d.f, d.R, nullptr, none, aux_off, wsums);
 }
@@ -187,14 +190,14 @@ int launch_lsq_plain(hipStream_t st, const LsqJob &job)
     return NMRFIT_OK;
 }
 
-bool rows_batch_lds(int32_t Pmax, size_t *lds, unsigned *aux_off)
+bool rows_batch_lds(int32_t Pmax, int fit_im, size_t *lds, unsigned *aux_off)
 {
     int v = NMRFIT_VARIANT_DEFAULT;
-    *lds = objective_lds(NMRFIT_VARIANT_DEFAULT, Pmax, true, 0, &v, aux_off, kWavesPerBlock, kWavesPerBlock, 0);
+    *lds = objective_lds(NMRFIT_VARIANT_DEFAULT, Pmax, true, fit_im, &v, aux_off, kWavesPerBlock, kWavesPerBlock, 0);
     return v == NMRFIT_VARIANT_DEFAULT && *lds + kObjectiveStaticLds + 16 <= 160 * 1024;
 }
 
-int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off)
+int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off, int fit_im)
 {
     if (K <= 0 || Smax <= 0) return NMRFIT_OK;
     const int64_t blocks_per_fit = (Smax + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -202,8 +205,13 @@ int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t 
         set_error("batch too large for one launch");
         return NMRFIT_E_INVALID;
     }
-    hipLaunchKernelGGL(residual_rows_batch_kernel, dim3((unsigned)(blocks_per_fit * K)), dim3(kWave * kWavesPerBlock), lds, st, d_fits,
-                       (int)blocks_per_fit, aux_off);
+    const dim3 grid((unsigned)(blocks_per_fit * K)), block(kWave * kWavesPerBlock);
+    if (fit_im == 0)
+        hipLaunchKernelGGL(residual_rows_batch_kernel<0>, grid, block, lds, st, d_fits, (int)blocks_per_fit, aux_off);
+    else if (fit_im == 1)
+        hipLaunchKernelGGL(residual_rows_batch_kernel<1>, grid, block, lds, st, d_fits, (int)blocks_per_fit, aux_off);
+    else
+        hipLaunchKernelGGL(residual_rows_batch_kernel<2>, grid, block, lds, st, d_fits, (int)blocks_per_fit, aux_off);
     NMRFIT_HIP(hipGetLastError());
     return NMRFIT_OK;
 }

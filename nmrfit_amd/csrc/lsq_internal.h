@@ -2,6 +2,7 @@
 // (nmrfit_batch_normal_equations): the per-fit records the kernels read and the launches.
 #pragma once
 #include "nmrfit_amd_lsq.h"
+#include "nmrfit_amd_lsq_im.h"
 #include "nmrfit_internal.h"
 
 namespace nmrfit {
@@ -46,7 +47,9 @@ int launch_lsq(hipStream_t st, const LsqJob *d_jobs, int32_t K, int32_t Dmax, bo
 int launch_lsq_plain(hipStream_t st, const LsqJob &job);
 
 // One fit of a residual-rows launch over a batch's resident spectra: the grid as BatchFit holds it, S parameter rows
-// X [S x D], their objective values f [S] and residual rows R [S x N].
+// X [S x D], their objective values f [S] and residual rows R [S x N].  A batch with an imaginary-channel mode may ask for
+// the rows of both channels instead (launch_rows_batch, fit_im 1 or 2): R is then [2][S][N], the imaginary rows second,
+// and f [S][2] the two RMSEs of every row.
 struct RowsFit {
     const double *wc, *u, *v, *wt;
     const double2 *chunk;
@@ -58,7 +61,7 @@ struct RowsFit {
     int32_t P, blk_chunks, n_blocks, pad;
 };
 // false: these peak counts leave the kernel's LDS records no room
-bool rows_batch_lds(int32_t Pmax, size_t *lds, unsigned *aux_off);
-int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off);
+bool rows_batch_lds(int32_t Pmax, int fit_im, size_t *lds, unsigned *aux_off);
+int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off, int fit_im);
 
 }  // namespace nmrfit

@@ -151,7 +151,11 @@ struct ObjectiveDeferred {
 struct PsoFused;
 constexpr int64_t kFusedMaxD = 400;   // 4 waves x D doubles of LDS for the updated rows (12.5 KiB at the limit)
 int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, double *df, double *dR,
-                     ObjectiveDeferred *defer = nullptr, const PsoFused *fused = nullptr);
+                     ObjectiveDeferred *defer = nullptr, const PsoFused *fused = nullptr, int rows_fit_im = 0);
+// rows_fit_im (1 or 2, with dR; include/nmrfit_amd_lsq_im.h): residual rows of both channels -- dR is [2][S][N], the
+// imaginary rows second, and df [S][2] receives the two RMSEs of every row.  DEFAULT kernel only: a context set to
+// another variant, or so many peaks that DEFAULT's LDS records do not fit, is NMRFIT_E_UNSUPPORTED.  Every other residual
+// launch sees the real channel alone, whatever the context's fit_im.
 int ensure(nmrfit_ctx *ctx, double **buf, int64_t *cap, int64_t need);
 // centred grid + per-chunk (min,max) table from the raw device copy of w
 int prepare_grid(nmrfit_ctx *ctx, const double *d_w_raw);

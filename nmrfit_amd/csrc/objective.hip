@@ -24,6 +24,23 @@ __global__ void finalize_kernel(const double *__restrict__ partial, int64_t S, i
 }
 
 // per-chunk (min, max) of the centred grid: one wave per chunk
+// residual rows of both channels (launch_objective, rows_fit_im): the two RMSEs of every row from the same per-block
+// sums in the same order -- 0.5 * (f2[2 i] + f2[2 i + 1]) is what finalize_kernel gives
+__global__ void finalize_rows_im_kernel(const double *__restrict__ partial, int64_t S, int64_t n_blocks, int64_t N,
+                                        double *__restrict__ f2)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S) return;
+    const double *p = partial + i * n_blocks * 2;
+    double ss = 0.0, si = 0.0;
+    for (int64_t c = 0; c < n_blocks; ++c) {
+        ss += p[2 * c];
+        si += p[2 * c + 1];
+    }
+    f2[2 * i] = sqrt(ss / (double)N);
+    f2[2 * i + 1] = sqrt(si / (double)N);
+}
+
 __global__ void chunk_minmax_kernel(const double *__restrict__ wc, int64_t N, int64_t n_chunks,
                                     double2 *__restrict__ out)
 {
@@ -138,10 +155,16 @@ size_t objective_lds(int variant, int32_t P, bool residual, int fit_im, int *var
 }
 
 int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, double *df, double *dR,
-                     ObjectiveDeferred *defer, const PsoFused *fused)
+                     ObjectiveDeferred *defer, const PsoFused *fused, int rows_fit_im)
 {
     if (defer) *defer = ObjectiveDeferred{};
-    const int fit_im = dR ? 0 : ctx->fit_im;
+    // residual rows see the real channel alone, except in the one call that asks for both (nmrfit_internal.h)
+    const bool rows_im = dR && rows_fit_im != 0;
+    if (rows_im && (defer || fused || (rows_fit_im != 1 && rows_fit_im != 2))) {
+        set_error("launch_objective: residual rows of both channels take fit_im 1 or 2 and no swarm update");
+        return NMRFIT_E_INVALID;
+    }
+    const int fit_im = rows_im ? rows_fit_im : dR ? 0 : ctx->fit_im;
     if (S == 0) return NMRFIT_OK;
     const int64_t N = ctx->N;
     // Segmenting: a wave is one (particle, segment) task; a segment is a whole number of blocks.  Swarms that already
@@ -204,6 +227,10 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     int wpb = kWavesPerBlock, slices = 0, rows = 0;
     copies(wpb, &slices, &rows);
     size_t lds = objective_lds(ctx->variant, P, dR != nullptr, fit_im, &variant, &aux_off, wpb, slices, rows);
+    if (rows_im && variant != NMRFIT_VARIANT_DEFAULT) {
+        set_error("residual rows with the imaginary channel exist for the DEFAULT kernel variant only (and while its LDS records fit)");
+        return NMRFIT_E_UNSUPPORTED;
+    }
     // Eight segments per particle (small swarms on short grids -- the reference's default 204 x 4096): an EIGHT-wave
     // workgroup is the particle, as the four-wave workgroup is for four segments: one prologue per particle, block
     // sums through LDS, f (and, in a swarm generation, the personal best) finished in this launch.
@@ -283,6 +310,20 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     la.aux_off = aux_off;
     la.wpb = wpb;
     int rc;
+    if (rows_im) {
+        rc = launch_objective_rows_im(la);
+        if (rc != NMRFIT_OK) return rc;
+        if (!direct_f) {
+            hipLaunchKernelGGL(finalize_rows_im_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream,
+                               ctx->d_partial, S, n_blocks, N, df);
+            NMRFIT_HIP(hipGetLastError());
+        }
+        ctx->last.waves = waves;
+        ctx->last.waves_per_workgroup = wpb;
+        ctx->last.nseg = (int32_t)nseg;
+        ctx->last.seg_len = seg_len;
+        return NMRFIT_OK;
+    }
     switch (variant) {   // one translation unit per selectable variant (they compile in parallel)
         case NMRFIT_VARIANT_DEFAULT: rc = launch_objective_default(la); break;
         case NMRFIT_VARIANT_FARFIELD: rc = launch_objective_farfield(la); break;

@@ -66,6 +66,12 @@ namespace {
 // FIT_IM: 0 real part only (reference default); 1 reference-compatible fit_im=True -- the
 // imaginary model is the LAST peak's dispersion only, because equations.py:199 assigns
 // instead of accumulating; 2 the imaginary model is the sum over all peaks.
+// WRITE_R with FIT_IM != 0 (objective_rows_im.hip, DEFAULT only; include/nmrfit_amd_lsq_im.h): the imaginary residual
+// ei = weights*(Id - If) is stored next to e, in a second plane of R_out ([2][S][N]), and `out` receives the two RMSEs of
+// every row ([S][2]) instead of their mean -- in all three geometries (one segment, workgroup = particle, partial sums +
+// finalize_rows_im_kernel).  Every statement of it sits under `if constexpr (WRITE_R && FIT_IM != 0)`: the other
+// instantiations compile to what they compiled to before.  Residual launches with FIT_IM of the other variants are
+// refused (NMRFIT_E_UNSUPPORTED).
 // Registers and occupancy of the selectable kernels (tools/kernel_resources.py, checked by
 // tests/test_kernel_resources_cpu.py; figures of the round-6 build): the headline objective kernel <DEFAULT, real part
 // only, four waves per workgroup> 127 VGPRs -- FOUR waves per SIMD, no scratch -- with the 8-peak group's 24 constants,
@@ -101,7 +107,8 @@ __device__ __forceinline__ void objective_body(
     int64_t seg_len, int blk_chunks, int seg_blocks /* blocks per segment */, int n_blocks_i /* blocks per grid */,
     double lane_step, double rec_devk,
     double *__restrict__ out,       // nseg == 1: f[S];  else per-block sums [S * n_blocks] (x2 with FIT_IM)
-    double *__restrict__ R_out,     // WRITE_R: residual rows [S*N]
+                                    // (WRITE_R with FIT_IM: the two RMSEs of every row, [S][2], where f would go)
+    double *__restrict__ R_out,     // WRITE_R: residual rows [S*N] (with FIT_IM: [2][S*N], the imaginary rows second)
     unsigned long long *__restrict__ clk,   // profiling only (else null): shader / reference clock of workgroup 0
     const PsoFused &upd,            // swarm generations: advance the particle first (x_in != null), X is then unused
     const unsigned aux_off,         // FIT_IM != 0: byte offset of the Dawson table in dynamic LDS
@@ -961,6 +968,10 @@ __device__ __forceinline__ void objective_body(
                 const double id = __builtin_fma(zr, vq[q], zi * uq[q]);  // Im((zr + i zi)(u + i v))
                 const double ei = tq[q] * (id - iacc[q]);
                 bs_im = __builtin_fma(ei, ei, bs_im);
+                // residual rows of both channels: the imaginary rows are the second plane of the same buffer
+                if constexpr (WRITE_R && FIT_IM != 0) {
+                    if (full || jl + q * kWave < j1) R_out[(S + particle) * N + jl + q * kWave] = ei;
+                }
             }
             if (WRITE_R && (full || jl + q * kWave < j1)) R_out[particle * N + jl + q * kWave] = e;
             const double nzr = __builtin_fma(zr, rr, -(zi * ri));         // z *= rho
@@ -1064,7 +1075,14 @@ __device__ __forceinline__ void objective_body(
             f = sqrt(ss / (double)N);
         else   // (rmse_real + rmse_imag) / 2, equations.py:205-209
             f = 0.5 * (sqrt(ss / (double)N) + sqrt(ss_im / (double)N));
-        if (lane == 0) out[particle] = f;
+        if constexpr (WRITE_R && FIT_IM != 0) {   // residual rows of both channels: the two RMSEs, not their mean (out: [S][2])
+            if (lane == 0) {
+                out[2 * particle] = sqrt(ss / (double)N);
+                out[2 * particle + 1] = sqrt(ss_im / (double)N);
+            }
+        } else {
+            if (lane == 0) out[particle] = f;
+        }
         // (no fused personal best here in a plain launch: one wave per particle means >= 16384 particles, where the swarm's
         // own select kernels are noise next to the objective -- and the call cost the headline kernel 12 bytes of scratch)
         if constexpr (WAVE_SWARM && !WRITE_R) {   // device-batched fits: the wave finishes its particle's step
@@ -1084,7 +1102,12 @@ __device__ __forceinline__ void objective_body(
                 if (FIT_IM != 0) ti += wsums[kMaxBlocks + c];
             }
             const double f = (FIT_IM == 0) ? sqrt(t / (double)N) : 0.5 * (sqrt(t / (double)N) + sqrt(ti / (double)N));
-            out[particle] = f;
+            if constexpr (WRITE_R && FIT_IM != 0) {   // (the same sums, each channel's RMSE on its own)
+                out[2 * particle] = sqrt(t / (double)N);
+                out[2 * particle + 1] = sqrt(ti / (double)N);
+            } else {
+                out[particle] = f;
+            }
             wsums[2 * kMaxBlocks] = f;
         }
         if constexpr (!WRITE_R) {
@@ -1158,6 +1181,10 @@ int launch_variant(const ObjectiveLaunch &a)
             NMRFIT_LAUNCH_W(false, 0, kWideWaves);
         else
             NMRFIT_LAUNCH(false, 0);
+    } else if (dR && fit_im != 0) {
+        // (residual rows of both channels: objective_rows_im.hip, DEFAULT only; launch_objective never comes here with them)
+        set_error("residual rows with the imaginary channel exist for the DEFAULT kernel variant only");
+        return NMRFIT_E_UNSUPPORTED;
     } else if (dR) {
         NMRFIT_LAUNCH(true, 0);
     } else if (fit_im == 0) {

@@ -47,6 +47,7 @@ int launch_objective_default(const ObjectiveLaunch &a);    // objective_default.
 int launch_objective_farfield(const ObjectiveLaunch &a);   // objective_farfield.hip
 int launch_objective_norec(const ObjectiveLaunch &a);      // objective_norec.hip
 int launch_objective_farfield32(const ObjectiveLaunch &a); // objective_farfield32.hip (objective launches, fit_im = 0)
+int launch_objective_rows_im(const ObjectiveLaunch &a);   // objective_rows_im.hip (DEFAULT, residual rows of both channels)
 #ifdef NMRFIT_AB_BUILD
 int launch_objective_ab(int variant, const ObjectiveLaunch &a);   // objective_ab.hip: BASELINE, NOSKIP, SINGLE, QUAD, STAGED
 #endif

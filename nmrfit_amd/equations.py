@@ -190,6 +190,39 @@ class Evaluator:
         out["f"] = float(out["f"][0])
         return out
 
+    # -- both channels (include/nmrfit_amd_lsq_im.h) -------------------------------------------
+    def residual_batch_im(self, X, fit_im):
+        """``(R_re, R_im, f2)``: the residual rows of both channels of the parameter rows ``X`` -- R_re what
+        ``residual_batch`` returns, R_im = weights*(I_data - I_fit) with I_fit of the mode ``fit_im`` (True / "sum") -- and
+        per row the two RMSEs (rho_re, rho_im) [B, 2]; their mean is ``objective_batch(X, fit_im)``."""
+        X, P = self._as_batch(X)
+        R = np.empty((2, X.shape[0], self.N), dtype=np.float64)
+        f2 = np.empty((X.shape[0], 2), dtype=np.float64)
+        _cabi.check(self._lib.nmrfit_residual_batch_im(self._ctx, X.shape[0], P, _cabi.ptr(X), fit_im_mode(fit_im),
+                                                       _cabi.ptr(R), _cabi.ptr(f2)))
+        return R[0], R[1], f2
+
+    def jacobian_im(self, rows, c, s, fit_im, J=False, r=False, normal=False):
+        """``nmrfit_jacobian_im``: ``jacobian`` per channel.  Returns a dict with what was asked for, every array with a
+        leading channel index (0 real, 1 imaginary) -- ``J`` [2, N, D], ``r`` [2, N], ``A`` [2, D, D], ``g`` [2, D]
+        (``normal``) -- and ``f2`` [2] = (rho_re, rho_im) of row 0."""
+        rows, P = self._as_batch(rows)
+        D = rows.shape[1]
+        c = _cabi.f64(c)
+        if rows.shape[0] != D + 1 or c.shape != (D,):
+            raise ValueError("jacobian_im: rows must be (D + 1) x D and c have D entries")
+        out = dict(f2=np.empty(2))
+        if J:
+            out["J"] = np.empty((2, self.N, D))
+        if r:
+            out["r"] = np.empty((2, self.N))
+        if normal:
+            out["A"], out["g"] = np.empty((2, D, D)), np.empty((2, D))
+        _cabi.check(self._lib.nmrfit_jacobian_im(self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s), fit_im_mode(fit_im),
+                                                 _cabi.ptr(out.get("J")), _cabi.ptr(out.get("r")), _cabi.ptr(out.get("A")),
+                                                 _cabi.ptr(out.get("g")), _cabi.ptr(out["f2"])))
+        return out
+
     # -- device-resident helpers (bench / swarm) ------------------------------------------
     def dev_alloc(self, nbytes):
         p = ctypes.c_void_p()

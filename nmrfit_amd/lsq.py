@@ -19,6 +19,14 @@ of a device batch in one go: ``FitBatch.normal_equations``), D^2 + D doubles per
 ``lm_polish`` is the small host loop over such D x D systems that refines K fits in lock step
 (``FitBatch.polish``, ``fit_many(batch_polish=True)``); ``normal_equations_host`` states the same quantities
 in numpy.
+
+Both channels (``nmrfit_jacobian_im``, include/nmrfit_amd_lsq_im.h).  A fit made with ``fit_im`` minimises
+f = (rho_re + rho_im)/2, the mean of the two channels' RMSEs (equations.py:205-209) -- a mean of two norms, not a sum of
+squares.  The device returns, per channel, the residual rows, J, r, A = J^T J, g = J^T r and rho; ``combine_channels``
+makes of them the gradient of f in the forward-difference model and a positive semi-definite matrix that dominates its
+Gauss-Newton Hessian, the ``(H, grad f, f)`` that ``lm_polish`` takes as it is.  ``ResidualModel(..., fit_im=mode)``,
+``polish(..., channels="both")``, ``FitBatch.polish(channels="both")`` and ``fit_many(batch_polish="both")`` are the ways in;
+every default is the real channel alone, as before.
 """
 import numpy as np
 
@@ -54,10 +62,51 @@ def normal_equations_host(R, c, s):
     return J.T @ J, J.T @ r, J, r
 
 
-class ResidualModel:
-    """fun / jac callables over an ``equations.Evaluator``."""
+def normal_equations_host_im(R_re, R_im, c, s):
+    """``normal_equations_host`` per channel: ``{"re": (A, g, rho), "im": (A, g, rho)}`` from the D + 1 residual rows of
+    either channel, rho = ||r|| the channel's RMSE at row 0 -- what ``nmrfit_jacobian_im`` returns, stated in numpy (A, g
+    and rho differ from the device's in summation order).  ``combine_channels`` takes the dict as it is."""
+    out = {}
+    for ch, R in (("re", R_re), ("im", R_im)):
+        A, g, _, r = normal_equations_host(R, c, s)
+        out[ch] = (A, g, float(np.sqrt(r @ r)))
+    return out
 
-    def __init__(self, evaluator, lower=None, upper=None, rel_step=_SQRT_EPS):
+
+def combine_channels(parts):
+    """``(H, grad, f)`` of the objective f = (rho_re + rho_im)/2 from its channels' normal equations.  ``parts``: a dict
+    with "re" and / or "im", or a sequence, of ``(A_ch, g_ch, rho_ch)`` with A_ch = J_ch^T J_ch, g_ch = J_ch^T r_ch and
+    rho_ch = ||r_ch||.  Since d rho/dx = J^T r / rho,
+        grad = (g_re/rho_re + g_im/rho_im)/2
+        H    = (A_re/rho_re + A_im/rho_im)/2
+    H is positive semi-definite and dominates the Gauss-Newton Hessian of f: the terms left out, -g g^T/rho^3 per channel,
+    are negative semi-definite.  ``lm_polish`` solves (H + lam diag H) d = -grad and accepts on f' < f: with this triple it
+    minimises the fit_im objective.  A channel whose rho is 0 or not finite contributes nothing to H and grad (it is at
+    its minimum, or lost); f is half the sum of the rhos as they are.  One channel alone gives today's (A, g, f) up to
+    the factor 1/(2 rho) on A and g -- which the relative damping cancels -- and f = rho/2.  Plain numpy."""
+    parts = list(parts.values()) if isinstance(parts, dict) else list(parts)
+    D = np.asarray(parts[0][1]).shape[0]
+    H = np.zeros((D, D))
+    grad = np.zeros(D)
+    f = 0.0
+    for A, g, rho in parts:
+        rho = float(rho)
+        f += 0.5 * rho
+        if np.isfinite(rho) and rho > 0.0:
+            H += np.asarray(A, dtype=np.float64) * (0.5 / rho)
+            grad += np.asarray(g, dtype=np.float64) * (0.5 / rho)
+    return H, grad, f
+
+
+class ResidualModel:
+    """fun / jac callables over an ``equations.Evaluator``.  ``fit_im`` 0 (default): the real channel, as ever.  With a
+    mode (True / "sum"): ``fun`` is the stacked 2N vector [r_re; r_im], ``jac`` the stacked 2N x D matrix (J_re above
+    J_im, one ``nmrfit_jacobian_im`` call) -- scipy's TRF then minimises rho_re^2 + rho_im^2 -- and ``normal_equations``
+    the combined ``(H, grad f, f)`` of the objective itself (``combine_channels``)."""
+
+    def __init__(self, evaluator, lower=None, upper=None, rel_step=_SQRT_EPS, fit_im=0):
+        from .equations import fit_im_mode
+        self.fit_im = fit_im_mode(fit_im)
         self.ev = evaluator
         self.N = evaluator.N
         self.lower = None if lower is None else _cabi.f64(lower)
@@ -69,6 +118,9 @@ class ResidualModel:
 
     def fun(self, x):
         self.n_fun += 1
+        if self.fit_im:
+            R_re, R_im, _ = self.ev.residual_batch_im(np.asarray(x, dtype=np.float64), self.fit_im)
+            return np.concatenate((R_re[0], R_im[0])) * self._scale
         return self.ev.residual_batch(np.asarray(x, dtype=np.float64))[0] * self._scale
 
     def steps(self, x):
@@ -91,6 +143,8 @@ class ResidualModel:
         device from them (csrc/lsq.hip) -- the bits of ``(R[1:] - R[0]) * (scale / h)`` transposed."""
         self.n_jac += 1
         rows, h = self.rows(x)
+        if self.fit_im:   # [2, N, D] as it arrives is J_re above J_im
+            return self.ev.jacobian_im(rows, self._scale / h, self._scale, self.fit_im, J=True)["J"].reshape(2 * self.N, -1)
         return self.ev.jacobian(rows, self._scale / h, self._scale, J=True)["J"]
 
     def normal_equations(self, x):
@@ -98,6 +152,9 @@ class ResidualModel:
         objective value the same launch returns for x.  D <= 76."""
         self.n_jac += 1
         rows, h = self.rows(x)
+        if self.fit_im:
+            out = self.ev.jacobian_im(rows, self._scale / h, self._scale, self.fit_im, normal=True)
+            return combine_channels([(out["A"][ch], out["g"][ch], out["f2"][ch]) for ch in (0, 1)])
         out = self.ev.jacobian(rows, self._scale / h, self._scale, normal=True)
         return out["A"], out["g"], out["f"]
 
@@ -105,12 +162,13 @@ class ResidualModel:
         return float(np.linalg.norm(self.fun(x)))
 
 
-def least_squares(evaluator, x0, lower, upper, **kwargs):
+def least_squares(evaluator, x0, lower, upper, fit_im=0, **kwargs):
     """scipy.optimize.least_squares with GPU residuals / Jacobian.  Returns the scipy result;
-    ``result.cost`` is 0.5*objective**2 and ``result.objective`` the RMSE the swarm minimises."""
+    ``result.cost`` is 0.5*objective**2 and ``result.objective`` the RMSE the swarm minimises.  ``fit_im`` (a mode):
+    the stacked residual of both channels -- ``result.objective`` is then sqrt(rho_re^2 + rho_im^2)."""
     from scipy.optimize import least_squares as _ls
     lower, upper = _cabi.f64(lower), _cabi.f64(upper)
-    model = ResidualModel(evaluator, lower, upper)
+    model = ResidualModel(evaluator, lower, upper, fit_im=fit_im)
     x0 = np.clip(np.asarray(x0, dtype=np.float64), lower, upper)
     kwargs.setdefault("method", "trf")
     kwargs.setdefault("x_scale", np.maximum(upper - lower, 1e-12))
@@ -120,14 +178,25 @@ def least_squares(evaluator, x0, lower, upper, **kwargs):
     return res
 
 
-def polish(evaluator, x_swarm, lower, upper, fit_im=False, **kwargs):
+def polish(evaluator, x_swarm, lower, upper, fit_im=False, channels="real", **kwargs):
     """Refine a swarm result; keeps it if the least-squares step does not improve on it.
 
     The residual rows are the REAL-part residual only.  ``fit_im`` is the mode the swarm
     minimised: acceptance and the returned value use that same objective
     (``objective_batch(x, fit_im=...)``), so a step that lowers the real-part RMSE but raises the
-    imaginary term is rejected and the meaning of the returned error never changes."""
+    imaginary term is rejected and the meaning of the returned error never changes.
+
+    ``channels="both"`` (with a ``fit_im`` mode): TRF on the stacked residual of both channels, [r_re; r_im] with
+    J_re above J_im -- it minimises rho_re^2 + rho_im^2 where the swarm minimised (rho_re + rho_im)/2, close relatives
+    with the same zero; acceptance is on the swarm's objective as above."""
     x_swarm = np.asarray(x_swarm, dtype=np.float64)
+    if channels not in ("real", "both"):
+        raise ValueError('polish: channels is "real" or "both"')
+    if channels == "both":
+        from .equations import fit_im_mode
+        if not fit_im_mode(fit_im):
+            raise ValueError('polish: channels="both" refines a fit_im objective: pass the fit\'s fit_im')
+        kwargs["fit_im"] = fit_im
     res = least_squares(evaluator, x_swarm, lower, upper, **kwargs)
     f0, f1 = (float(f) for f in evaluator.objective_batch(np.stack([x_swarm, res.x]), fit_im=fit_im))
     if f1 <= f0:
@@ -150,6 +219,24 @@ def rows_provider(residuals, lowers, uppers, rel_step=_SQRT_EPS):
             s = 1.0 / np.sqrt(R.shape[1])
             A, g, _, _ = normal_equations_host(R, s / h, s)
             out.append((A, g, float(f[0])))
+        return out
+    return provider
+
+
+def rows_provider_im(residuals, lowers, uppers, rel_step=_SQRT_EPS):
+    """``rows_provider`` on both channels: ``residuals[k](rows) -> (R_re, R_im)`` ([(D + 1) x N] each: a host
+    restatement, or ``Evaluator.residual_batch_im(rows, mode)[:2]``); per fit the combined ``(H, grad f, f)`` of
+    f = (rho_re + rho_im)/2 by ``normal_equations_host_im`` and ``combine_channels``."""
+    def provider(X):
+        out = []
+        for k, x in enumerate(X):
+            if x is None:
+                out.append(None)
+                continue
+            rows, h = forward_rows(x, lowers[k], uppers[k], rel_step)
+            R_re, R_im = residuals[k](rows)[:2]
+            s = 1.0 / np.sqrt(R_re.shape[1])
+            out.append(combine_channels(normal_equations_host_im(R_re, R_im, s / h, s)))
         return out
     return provider
 
