@@ -12,6 +12,10 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.shift_phase_many(datas, method='auto')            Data.shift_phase for many spectra: the phase search on the DEVICE
     nmrfit_amd.select_peaks_many(datas, method='auto')           Data.select_peaks for many spectra: peak picking on the DEVICE
     nmrfit_amd.utils.compute_weights_many(ws, peaks_list)        FitUtility._compute_weights for many spectra on the DEVICE
+    nmrfit_amd.fit_replicas(data, lower, upper, replicas=32, sigma=...)   noise-replica uncertainty: the noisy copies made on the
+                                                                 DEVICE, all refits one batch -> ReplicaFits (area_fraction_std, ...)
+    nmrfit_amd.fit_replicas_many(jobs, replicas=32)              the same for several spectra, packed into ragged batches
+    nmrfit_amd.noise.replicas(us, vs, sigma_u, sigma_v, seeds)   the noisy copies alone (noise.normals / replicas_host: the numpy mirror)
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
@@ -23,7 +27,8 @@ bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
-from . import batch, containers, equations, peaks, proc_autophase, pso, synth, utils  # noqa: F401
+from . import batch, containers, equations, noise, peaks, proc_autophase, pso, synth, utils  # noqa: F401
+from .noise import fit_replicas, fit_replicas_many  # noqa: F401
 from .containers import Data, select_peaks_many, shift_phase_many  # noqa: F401
 
 __version__ = "0.1.0"

@@ -170,6 +170,13 @@ LSQ_IM_SIGNATURES = {
     "nmrfit_jacobian_im": [_VP, _I32, _VP, _VP, ctypes.c_double, _INT, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_batch_normal_equations_im": [_VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# NOISE_SIGNATURES: include/nmrfit_amd_noise.h (noise replicas of spectra made on the device, out of place or in place on
+# a batch's resident spectra; the spectrum a fit of a batch is fitting)
+NOISE_SIGNATURES = {
+    "nmrfit_noise_replicas": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_add_noise": [_VP, _VP, _VP, _VP],
+    "nmrfit_batch_spectrum": [_VP, _I32, _VP, _VP],
+}
 LSQ_MAX_D = 76                    # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -274,7 +281,7 @@ def lib():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
-                + list(LSQ_IM_SIGNATURES.items()):
+                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

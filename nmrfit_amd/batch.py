@@ -183,6 +183,29 @@ class FitBatch:
                             V=f4[0], I=f4[1], u=f4[2], v=f4[3], data_V=d2[0], data_I=d2[1]))
         return out
 
+    # -- noise replicas (include/nmrfit_amd_noise.h) -----------------------------------------------
+    def add_noise(self, sigma_u, sigma_v, seeds):
+        """Perturb the resident spectra in place on the device: fit k's ``u, v`` become
+        ``u + sigma_u[k] * z_u, v + sigma_v[k] * z_v`` with the deviates of noise seed ``seeds[k]`` (csrc/noise.hip; the
+        numpy mirror is ``noise.replicas_host``) -- bit for bit what ``noise.replicas`` returns for the uploaded arrays.
+        Scalars broadcast to the K fits; a fit whose two sigmas are 0 is not touched.  Allowed once, and only before the
+        first generation (``NmrfitError`` with the state code otherwise)."""
+        su = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.K,)))
+        sv = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (self.K,)))
+        sd = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in (seeds if np.ndim(seeds) else [seeds] * self.K)], dtype=np.uint64)
+        if sd.shape != (self.K,):
+            raise ValueError("FitBatch.add_noise: one seed per fit")
+        _cabi.check(self._lib.nmrfit_batch_add_noise(self._h, _cabi.ptr(su), _cabi.ptr(sv), _cabi.ptr(sd)))
+
+    def spectrum(self, k):
+        """``(u, v)`` of the spectrum fit ``k`` is fitting, in grid order: what was uploaded, or its replica after
+        ``add_noise``.  Any state."""
+        k = int(k)
+        n = int(self.Ns[k]) if 0 <= k < self.K else 1
+        u, v = np.empty(n), np.empty(n)
+        _cabi.check(self._lib.nmrfit_batch_spectrum(self._h, k, _cabi.ptr(u), _cabi.ptr(v)))
+        return u, v
+
     # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
     def normal_equations(self, X, channels="real"):
         """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``

@@ -19,7 +19,9 @@
 #include "host_call.h"
 #include "lsq_internal.h"
 #include "nmrfit_amd_diag.h"
+#include "nmrfit_amd_noise.h"
 #include "nmrfit_amd_prep.h"
+#include "noise_internal.h"
 #include "result_internal.h"
 #include "weights_internal.h"
 
@@ -69,6 +71,7 @@ struct BatchPart {
     int xp = 0, b = 0;
     bool fold_pending = false;
     bool initialized = false;
+    bool noised = false;                 // nmrfit_batch_add_noise has perturbed the resident u, v (allowed once)
     int64_t launches = 0;
 };
 
@@ -1044,6 +1047,45 @@ static int part_get_state(BatchPart *b, int32_t k, double *x, double *v, double 
     return NMRFIT_OK;
 }
 
+// include/nmrfit_amd_noise.h for the fits of a part: one launch of the noise kernel (noise.hip) on the part's stream, in
+// place on the resident u and v planes -- point j at grid_slot(j), j < N_k: the padding stays zero.  Nothing else of a
+// BatchFit depends on u or v (w0, wspan, lane_step, rec_devk and the chunk table are the grid's).  sigma_u, sigma_v,
+// seed: this part's shares, already checked.  The job table goes with `mem`; the caller synchronises.
+static int part_add_noise_enqueue(BatchPart *b, const double *sigma_u, const double *sigma_v, const uint64_t *seed, Scratch &mem)
+{
+    int rc = bind_batch(b);
+    if (rc != NMRFIT_OK) return rc;
+    std::vector<NoiseJob> jobs((size_t)b->K);
+    for (int32_t k = 0; k < b->K; ++k) {
+        const BatchFit &f = b->h_fits[(size_t)k];
+        double *u = const_cast<double *>(f.u), *v = const_cast<double *>(f.v);
+        jobs[(size_t)k] = NoiseJob{u, v, u, v, f.N, sigma_u[k], sigma_v[k], seed[k]};
+    }
+    NoiseJob *d_jobs = nullptr;
+    NMRFIT_HIP(mem.alloc(&d_jobs, jobs.size()));
+    // (pageable host memory: the copy has left `jobs` when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(NoiseJob), hipMemcpyHostToDevice, b->stream));
+    return launch_noise(b->stream, d_jobs, b->K, b->Nmax, true);
+}
+
+// the two planes of fit k as the kernels see them, back in grid order (the inverse of batch_prepare_kernel's scatter)
+static int part_spectrum(BatchPart *b, int32_t k, double *u_out, double *v_out)
+{
+    int rc = bind_batch(b);
+    if (rc != NMRFIT_OK) return rc;
+    const BatchFit &f = b->h_fits[(size_t)k];
+    Scratch mem;
+    double *d_out = nullptr;   // [2][N]
+    const size_t n = (size_t)f.N;
+    NMRFIT_HIP(mem.alloc(&d_out, 2 * n));
+    rc = launch_noise_gather(b->stream, f.u, f.v, f.N, d_out, d_out + n);
+    if (rc == NMRFIT_OK && u_out) rc = staged_d2h(b->device, b->stream, u_out, d_out, n * sizeof(double));
+    if (rc == NMRFIT_OK && v_out) rc = staged_d2h(b->device, b->stream, v_out, d_out + n, n * sizeof(double));
+    const hipError_t e = hipStreamSynchronize(b->stream);   // (before `mem` frees what the launch writes)
+    if (rc == NMRFIT_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(spectrum)", __FILE__, __LINE__);
+    return rc;
+}
+
 
 // ---- the batch: its fits divided over one or two parts, each with a stream of its own ---------------------------------
 // A generation of a part is a few lock-step rounds of short waves: its last round drains with the SIMDs
@@ -1387,6 +1429,52 @@ int nmrfit_batch_geometry(const nmrfit_batch *b, int32_t *mode, int32_t *waves_p
     }
     if (workgroups) *workgroups = total;
     return NMRFIT_OK;
+}
+
+/* ---- noise replicas (include/nmrfit_amd_noise.h) ---- */
+
+int nmrfit_batch_add_noise(nmrfit_batch *b, const double *sigma_u, const double *sigma_v, const uint64_t *seed)
+{
+    int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    if ((rc = check_noise_args("nmrfit_batch_add_noise", b->K, sigma_u, sigma_v, seed)) != NMRFIT_OK) return rc;
+    for (const BatchPart *q : b->parts) {
+        if (q->initialized || q->noised) {
+            set_error(q->noised ? "nmrfit_batch_add_noise: noise was already added to this batch"
+                                : "nmrfit_batch_add_noise after the first generation");
+            return NMRFIT_E_STATE;
+        }
+        if (q->d_result) {
+            set_error("nmrfit_batch_add_noise: a reconstruction of this batch is still in flight");
+            return NMRFIT_E_STATE;
+        }
+    }
+    // From here on the batch counts as perturbed, every part of it: should a part's launch fail, the others may have run, the
+    // spectra are then neither the upload nor the replica, and a second call must not add noise to the parts that did.
+    for (BatchPart *q : b->parts) q->noised = true;
+    // every part enqueues its launch on its own stream; then all are waited for (the job tables go with `mem` after that)
+    Scratch mem;
+    for (size_t p = 0; p < b->parts.size() && rc == NMRFIT_OK; ++p) {
+        const int32_t f0 = b->first[p];
+        rc = part_add_noise_enqueue(b->parts[p], sigma_u + f0, sigma_v + f0, seed + f0, mem);
+    }
+    for (BatchPart *q : b->parts) {
+        const hipError_t e = hipStreamSynchronize(q->stream);
+        if (rc == NMRFIT_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(noise)", __FILE__, __LINE__);
+    }
+    return rc;
+}
+
+int nmrfit_batch_spectrum(nmrfit_batch *b, int32_t k, double *u_out, double *v_out)
+{
+    int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    if (k < 0 || k >= b->K) {
+        set_error("nmrfit_batch_spectrum: fit index out of range");
+        return NMRFIT_E_INVALID;
+    }
+    const int q = part_of(b, k);
+    return part_spectrum(b->parts[(size_t)q], k - b->first[(size_t)q], u_out, v_out);
 }
 
 int nmrfit_batch_synchronize(nmrfit_batch *b)
