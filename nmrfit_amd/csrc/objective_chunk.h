@@ -34,9 +34,12 @@ __device__ __forceinline__ void lorentz_tree(const double (&a)[G], const double 
     }
 }
 
-template <int G>
+// INIT (every group function below): this call is the first of the chunk to touch the accumulators -- they are not
+// read, and `base` (the particle's offset term, a scalar pair) is the addend of the group's final FMA instead:
+// fma(a, r, base) either way, bit for bit, without eight register moves per chunk to set the accumulators first.
+template <int G, bool INIT = false>
 __device__ __forceinline__ void lorentz_group(const PeakLor *r, const double (&wv)[kPointsPerLane],
-                                              double (&acc)[kPointsPerLane])
+                                              double (&acc)[kPointsPerLane], const double base = 0.0)
 {
     double ih[G], c[G], a[G];
 #pragma unroll
@@ -58,7 +61,7 @@ __device__ __forceinline__ void lorentz_group(const PeakLor *r, const double (&w
         }
         double num, den;
         lorentz_tree<G, 0, G>(a, s, num, den);
-        acc[q] = __builtin_fma(num, rcp64(den), acc[q]);
+        acc[q] = __builtin_fma(num, rcp64(den), INIT ? base : acc[q]);
         if ((q + 1) % kInterleave == 0) __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -68,9 +71,9 @@ __device__ __forceinline__ void lorentz_group(const PeakLor *r, const double (&w
 // reciprocals combines in TWO operations, 1/s0 + 1/s1 = (s0 + s1)/(s0 s1), instead of three,
 // so a group of 8 costs 16 + 8 + 6 + 3 + 4 = 37 operations per point instead of 41.  Staging
 // marks the groups for which this is safe (PeakFast::ok); the others take lorentz_group.
-template <int G>
+template <int G, bool INIT = false>
 __device__ __forceinline__ void lorentz_group_fast(const PeakFast *r, const double (&wv)[kPointsPerLane],
-                                                   double (&acc)[kPointsPerLane])
+                                                   double (&acc)[kPointsPerLane], const double base = 0.0)
 {
     static_assert(G % 2 == 0, "pairs");
     double ih[G], c[G], ia[G];
@@ -115,18 +118,19 @@ __device__ __forceinline__ void lorentz_group_fast(const PeakFast *r, const doub
         const double p23 = d2 * d3, a2 = n2 * d3, a3 = n3 * d2;
         const double r = rcp64(p01 * p23);
         const double r01 = r * p23, r23 = r * p01;
-        acc[q0] = __builtin_fma(a0, r01, acc[q0]);
-        acc[q0 + 1] = __builtin_fma(a1, r01, acc[q0 + 1]);
-        acc[q0 + 2] = __builtin_fma(a2, r23, acc[q0 + 2]);
-        acc[q0 + 3] = __builtin_fma(a3, r23, acc[q0 + 3]);
+        acc[q0] = __builtin_fma(a0, r01, INIT ? base : acc[q0]);
+        acc[q0 + 1] = __builtin_fma(a1, r01, INIT ? base : acc[q0 + 1]);
+        acc[q0 + 2] = __builtin_fma(a2, r23, INIT ? base : acc[q0 + 2]);
+        acc[q0 + 3] = __builtin_fma(a3, r23, INIT ? base : acc[q0 + 3]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
 // A single peak in the scaled form (the odd one out of a short tail group): 1/s' per point, one
 // reciprocal per four points.
+template <bool INIT = false>
 __device__ __forceinline__ void lorentz_one_fast(const PeakFast *r, const double (&wv)[kPointsPerLane],
-                                                 double (&acc)[kPointsPerLane])
+                                                 double (&acc)[kPointsPerLane], const double base = 0.0)
 {
     const double ih = r->ihs, c = r->cs, ia = r->ia;
 #pragma unroll
@@ -140,25 +144,39 @@ __device__ __forceinline__ void lorentz_one_fast(const PeakFast *r, const double
         const double p01 = s[0] * s[1], p23 = s[2] * s[3];
         const double rr = rcp64(p01 * p23);
         const double a01 = rr * p23, a23 = rr * p01;
-        acc[q0] = __builtin_fma(a01, s[1], acc[q0]);
-        acc[q0 + 1] = __builtin_fma(a01, s[0], acc[q0 + 1]);
-        acc[q0 + 2] = __builtin_fma(a23, s[3], acc[q0 + 2]);
-        acc[q0 + 3] = __builtin_fma(a23, s[2], acc[q0 + 3]);
+        acc[q0] = __builtin_fma(a01, s[1], INIT ? base : acc[q0]);
+        acc[q0 + 1] = __builtin_fma(a01, s[0], INIT ? base : acc[q0 + 1]);
+        acc[q0 + 2] = __builtin_fma(a23, s[3], INIT ? base : acc[q0 + 2]);
+        acc[q0 + 3] = __builtin_fma(a23, s[2], INIT ? base : acc[q0 + 3]);
     }
 }
 
-// The short tail group (1..7 peaks) in the scaled form: an even-sized group, then the odd peak.
+// The short tail group (1..7 peaks) in the scaled form: an even-sized group, then the odd peak.  With INIT the tail is
+// the chunk's first call (a particle of fewer than 8 peaks): whichever step runs first starts the accumulators.
+template <bool INIT = false>
 __device__ __forceinline__ void lorentz_tail_fast(int n, const PeakFast *r, const double (&wv)[kPointsPerLane],
-                                                  double (&acc)[kPointsPerLane])
+                                                  double (&acc)[kPointsPerLane], const double base = 0.0)
 {
     const int even = n & ~1;
-    if (even == 6)
-        lorentz_group_fast<6>(r, wv, acc);
-    else if (even == 4)
-        lorentz_group_fast<4>(r, wv, acc);
-    else if (even == 2)
-        lorentz_group_fast<2>(r, wv, acc);
-    if (n & 1) lorentz_one_fast(r + even, wv, acc);
+    if constexpr (INIT) {
+        if (even == 6)
+            lorentz_group_fast<6, true>(r, wv, acc, base);
+        else if (even == 4)
+            lorentz_group_fast<4, true>(r, wv, acc, base);
+        else if (even == 2)
+            lorentz_group_fast<2, true>(r, wv, acc, base);
+        else
+            lorentz_one_fast<true>(r, wv, acc, base);   // (n == 1: the odd peak is the chunk's first)
+        if (even != 0 && (n & 1)) lorentz_one_fast(r + even, wv, acc);
+    } else {
+        if (even == 6)
+            lorentz_group_fast<6>(r, wv, acc);
+        else if (even == 4)
+            lorentz_group_fast<4>(r, wv, acc);
+        else if (even == 2)
+            lorentz_group_fast<2>(r, wv, acc);
+        if (n & 1) lorentz_one_fast(r + even, wv, acc);
+    }
 }
 
 // One peak over the lane's points with one reciprocal per four points (batch inversion; with
@@ -186,15 +204,15 @@ __device__ __forceinline__ void lorentz_one(const PeakLor *r, const double (&wv)
 }
 
 // group of a run-time size 1..GMAX-1 (tail of a pass)
-template <int GMAX>
+template <int GMAX, bool INIT = false>
 __device__ __forceinline__ void lorentz_tail(int n, const PeakLor *r, const double (&wv)[kPointsPerLane],
-                                             double (&acc)[kPointsPerLane])
+                                             double (&acc)[kPointsPerLane], const double base = 0.0)
 {
     if constexpr (GMAX > 1) {
         if (n == GMAX - 1)
-            lorentz_group<GMAX - 1>(r, wv, acc);
+            lorentz_group<GMAX - 1, INIT>(r, wv, acc, base);
         else
-            lorentz_tail<GMAX - 1>(n, r, wv, acc);
+            lorentz_tail<GMAX - 1, INIT>(n, r, wv, acc, base);
     }
 }
 

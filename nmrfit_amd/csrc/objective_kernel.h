@@ -605,10 +605,10 @@ __device__ __forceinline__ void objective_body(
             for (int q = 0; q < kPointsPerLane; ++q)
                 wv[q] = (jl + q * kWave < j1) ? wc[jb + (q >> 1) * (2 * kWave) + 2 * lane + (q & 1)] : 0.0;
         }
-#pragma unroll
-        for (int q = 0; q < kPointsPerLane; ++q) acc[q] = base;
-
+        // (the accumulators are not set here: whatever touches them first in this chunk starts them from `base`)
         if (VARIANT == NMRFIT_VARIANT_BASELINE) {
+#pragma unroll
+            for (int q = 0; q < kPointsPerLane; ++q) acc[q] = base;
             for (int k = 0; k < P; ++k) {
                 const PeakLor rec = lor[k];
 #pragma unroll
@@ -693,12 +693,13 @@ __device__ __forceinline__ void objective_body(
                         horner_done = true;
                     }
                     for (unsigned m = near_c; m; m &= m - 1) lorentz_one(lor + __builtin_ctz(m), wv, acc);
-                    if (kRec && full && rec_all) {
-                        for (unsigned m = hits_c; m; m &= m - 1) gauss_add_rec(lor + __builtin_ctz(m), grec + __builtin_ctz(m), wv, acc);
-                    } else {
-                        for (unsigned m = hits_c; m; m &= m - 1) gauss_add<true>(lor + __builtin_ctz(m), wv, acc);
-                    }
+                    // (one loop after the other, the mask to one of them: see the direct form below)
+                    const bool rec = kRec && full && rec_all;
+                    for (unsigned m = rec ? hits_c : 0u; m; m &= m - 1) gauss_add_rec(lor + __builtin_ctz(m), grec + __builtin_ctz(m), wv, acc);
+                    for (unsigned m = rec ? 0u : hits_c; m; m &= m - 1) gauss_add<true>(lor + __builtin_ctz(m), wv, acc);
                 } else {
+#pragma unroll
+                for (int q = 0; q < kPointsPerLane; ++q) acc[q] = base;   // (more than 32 peaks: the near peaks come before the polynomial)
                 double csum = 0.0;    // lane l: coefficient of order l >> 2 (all 4 lanes of a quad)
                 for (int kb = 0; kb < P; kb += kWave) {
                     const int k = kb + lane;
@@ -779,7 +780,31 @@ __device__ __forceinline__ void objective_body(
                 }
                 }
                 wave_lds_fence();
-            } else
+            } else {
+            // The chunk's FIRST Lorentzian call starts the accumulators (INIT, objective_chunk.h): it takes `base` as the
+            // addend of its final FMAs instead of finding it in accumulators set by eight moves beforehand.  Which call
+            // that is is decided here, once per chunk, ahead of the pass loop: the first full group, or the short group
+            // of a particle with fewer peaks than one.  Without a peak the accumulators are the offset alone.
+            int k = 0;
+            {
+                const int kend0 = (P < kWave) ? P : kWave;
+                if (kGroup <= kend0) {
+                    if constexpr (kFastLoop)
+                        lorentz_group_fast<kGroup, true>(lorf, wv, acc, base);
+                    else
+                        lorentz_group<kGroup, true>(lor, wv, acc, base);
+                    k = kGroup;
+                } else if (kend0 > 0) {
+                    if constexpr (kFastLoop)
+                        lorentz_tail_fast<true>(kend0, lorf, wv, acc, base);
+                    else
+                        lorentz_tail<kGroup, true>(kend0, lor, wv, acc, base);
+                    k = kend0;
+                } else {
+#pragma unroll
+                    for (int q = 0; q < kPointsPerLane; ++q) acc[q] = base;
+                }
+            }
             for (int kb = 0; kb < P; kb += kWave) {
                 const int kend = (P < kb + kWave) ? P : kb + kWave;
                 // which of peaks kb..kb+63 have their Gaussian window inside this chunk's
@@ -795,7 +820,7 @@ __device__ __forceinline__ void objective_body(
                 }
                 // Lorentzians first, in straight-line groups; then the (few) Gaussians whose
                 // window touches this chunk, one scalar loop over the set bits of the mask
-                int k = kb;
+                if (kb != 0) k = kb;   // (the first pass: behind the call that started the accumulators)
                 if constexpr (kFastLoop) {
                     for (; k + kGroup <= kend; k += kGroup) lorentz_group_fast<kGroup>(lorf + k, wv, acc);
                     if (k < kend) lorentz_tail_fast(kend - k, lorf + k, wv, acc);
@@ -804,13 +829,16 @@ __device__ __forceinline__ void objective_body(
                     if (k < kend) lorentz_tail<kGroup>(kend - k, lor + k, wv, acc);   // one smaller group
                 }
                 if (kend - kb < kWave) hits &= (1ull << (kend - kb)) - 1ull;
-                if (kRec && full && rec_all) {
-                    for (unsigned long long m = hits; m; m &= m - 1) {
-                        const int k1 = kb + __builtin_ctzll(m);
-                        gauss_add_rec(lor + k1, grec + k1, wv, acc);
-                    }
-                } else
-                for (unsigned long long m = hits; m; m &= m - 1) gauss_add<kSkip>(lor + kb + __builtin_ctzll(m), wv, acc);
+                // (two loops one after the other, each an update of the accumulators in place, and the mask goes to one of
+                // them: as the two arms of a branch they met in a second set of the eight accumulators, filled by eight
+                // moves per chunk whether a peak hit or not)
+                const bool rec = kRec && full && rec_all;
+                for (unsigned long long m = rec ? hits : 0ull; m; m &= m - 1) {
+                    const int k1 = kb + __builtin_ctzll(m);
+                    gauss_add_rec(lor + k1, grec + k1, wv, acc);
+                }
+                for (unsigned long long m = rec ? 0ull : hits; m; m &= m - 1) gauss_add<kSkip>(lor + kb + __builtin_ctzll(m), wv, acc);
+            }
             }
         }
 
