@@ -1,6 +1,6 @@
 """
 Device-batched fits: K independent spectra fitted together, one kernel launch per swarm generation for all of them
-(``nmrfit_batch_*`` of libnmrfit_amd.so, csrc/batch.hip).
+(``nmrfit_batch_*`` of libnmrfit_amd.so, csrc/batch*.hip).
 
 The reference's users call ``nmrfit.fit`` once per spectrum (nmrfit/core.py:64, README.md:64-66), each fit a
 204-particle swarm (nmrfit/utils.py:177) -- a fraction of an MI355X.  ``FitBatch`` holds K spectra -- of any lengths:

@@ -47,7 +47,7 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
 
     * ``batch=True`` (default): jobs of equal kernel variant, ``fit_im``, ``maxiter`` and ``check_every`` -- grid lengths,
       peak counts and swarm sizes may differ -- are fitted as ONE device batch -- one kernel launch per swarm generation for all of them (nmrfit_amd.batch.FitBatch,
-      csrc/batch.hip).  A 204-particle swarm fills a fraction of an MI355X; a batch fills it.  Each fit's ``params`` and
+      csrc/batch*.hip).  A 204-particle swarm fills a fraction of an MI355X; a batch fills it.  Each fit's ``params`` and
       ``error`` are bit-identical to what ``fit`` returns for it alone with the same ``options['seed']``.  Job lists go
       through batches of a quarter of the list, between 40 and 200 jobs (``nmrfit_amd.core.BATCH_JOBS`` overrides),
       three stages in flight: a second host thread prepares the next batch (error weights, plans, device state) while

@@ -1,4 +1,4 @@
-// batch_internal.h -- shared by batch.hip (host side of the device-batched fits) and objective_batch.hip (the kernel
+// batch_internal.h -- shared by the host side of the device-batched fits (batch_part.h) and objective_batch*.hip (the kernel
 // instantiations): the per-fit descriptor the batched objective kernel reads, and the launch record.
 #pragma once
 #include "objective_launch.h"
@@ -7,7 +7,7 @@ namespace nmrfit {
 
 // One fit of a batch, as the kernel sees it: its spectrum (the `args=(w, u, v, weights)` tuple of nmrfit/utils.py:176,
 // prepared like a context's arrays: centred, padded, grid_slot order), its peak count and its swarm.  Lives in device
-// memory, one table of K records per buffer phase (batch.hip): the kernel finds its record from blockIdx alone.
+// memory, one table of K records per buffer phase (batch_create.hip): the kernel finds its record from blockIdx alone.
 struct BatchFit {
     const double *wc, *u, *v, *wt;
     const double2 *chunk;

@@ -358,7 +358,7 @@ int nmrfit_ctx_create(int device, int64_t N, const double *w, const double *u, c
     ctx->device = device;
     ctx->compute_units = prop.cus;
     ctx->N = N;
-    ctx->n_chunks = (N + kChunk - 1) / kChunk;
+    ctx->n_chunks = block_plan(N).n_chunks;
     if (const char *tw = getenv("NMRFIT_TARGET_WAVES")) ctx->target_waves = atoll(tw);   // tuning knob
     if (getenv("NMRFIT_NO_WIDE_WORKGROUPS")) ctx->wide_workgroups = false;               // A/B knob
     // test knob: run a whole test suite with another kernel variant as every context's default
@@ -563,7 +563,7 @@ int nmrfit_objective_batch(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *
 
 // The reconstruction of ONE fit through the kernel of result.hip: scratch device memory for the parameter vector, the
 // optional output grid and the outputs, one launch, the copies back.  (A device batch does the same for all its fits in
-// one launch from its resident state: nmrfit_batch_contributions, batch.hip.)
+// one launch from its resident state: nmrfit_batch_contributions, batch_data.hip.)
 static int generate_one(nmrfit_ctx *ctx, int32_t P, const double *x, int64_t Nout, const double *w_out, double *real_out,
                         double *imag_out, double *fit_out, double *data_out, const char *who)
 {

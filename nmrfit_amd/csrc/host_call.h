@@ -21,16 +21,30 @@ namespace nmrfit {
         }                                                                             \
     } while (0)
 
+// a refusal: the message recorded, the code returned
+inline int refuse(int code, const std::string &msg)
+{
+    set_error(msg);
+    return code;
+}
+
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // one allocation cut into 256-byte aligned pieces: take() returns a piece's byte offset, total is what to allocate
 struct Carver {
     size_t total = 0;
     size_t take(size_t bytes)
     {
         const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
+        total += align256(bytes);
         return at;
     }
 };
+
+// One copy of a swarm's state block -- (fg, best_f, g[D], best_x[D] | generations, stop code), the two flags right behind
+// the doubles -- as a lone swarm (pso.hip) and a fit of a batch (batch_create.hip) hold it, twice each: the deferred fold of a
+// fused launch reads one copy and writes the other (PsoFused::flip).
+inline size_t swarm_state_bytes(int64_t D) { return align256((size_t)(2 + 2 * D) * sizeof(double) + 2 * sizeof(long long)); }
 
 // device buffers of one call, freed on every path
 struct Scratch {

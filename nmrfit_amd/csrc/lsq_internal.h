@@ -1,5 +1,5 @@
-// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), cabi.hip (nmrfit_jacobian) and batch.hip
-// (nmrfit_batch_normal_equations): the per-fit records the kernels read and the launches.
+// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), cabi.hip (nmrfit_jacobian) and
+// batch_lsq.hip (nmrfit_batch_normal_equations*): the per-fit records the kernels read and the launches.
 #pragma once
 #include "nmrfit_amd_lsq.h"
 #include "nmrfit_amd_lsq_im.h"

@@ -19,7 +19,24 @@ constexpr int kBlock = kWave * kWavesPerBlock;
 constexpr int kPointsPerLane = NMRFIT_POINTS;    // grid points register-blocked per lane per chunk
 constexpr int kChunk = kWave * kPointsPerLane;   // 512 grid points per wave per chunk
 constexpr int kMaxBlocks = 16;       // blocks per grid: the unit of the canonical summation order and of the phase
-                                     // re-seeding (blk_chunks = ceil(n_chunks / 16)); objective.hip, pso_update.h
+                                     // re-seeding (block_plan below); pso_update.h
+// The block structure of a grid of N points: a function of N ALONE, so that a fit's sums do not depend on the swarm, the
+// launch geometry, sharding, or on whether it runs alone or in a batch.  Every host-side user takes it from here.
+struct BlockPlan {
+    int64_t n_chunks;    // chunks of kChunk points
+    int blk_chunks;      // chunks per block
+    int64_t n_blocks;    // blocks per grid (<= kMaxBlocks)
+    int64_t blk_len;     // points per block
+};
+inline BlockPlan block_plan(int64_t N)
+{
+    BlockPlan p;
+    p.n_chunks = (N + kChunk - 1) / kChunk;
+    p.blk_chunks = (int)((p.n_chunks + kMaxBlocks - 1) / kMaxBlocks);
+    p.n_blocks = (p.n_chunks + p.blk_chunks - 1) / p.blk_chunks;
+    p.blk_len = (int64_t)p.blk_chunks * kChunk;
+    return p;
+}
 constexpr int kMaxPeaks = 960;       // LDS: one copy of the per-peak records per wave when the waves of a workgroup hold different
                                      // particles -- 4 x P x (32 B PeakLor + 8 B PeakWin [+ 16 B recurrence + 32 B PeakFast, dropped
                                      // above P ~ 450]) -- + block seeds, per-wave lane phase seeds, the Dawson table <= 160 KiB
@@ -39,6 +56,26 @@ __host__ __device__ inline int64_t grid_slot(int64_t j)
     return (j - o) + (q >> 1) * (2 * kWave) + 2 * l + (q & 1);
 }
 static_assert(kWave == 64 && kPointsPerLane % 2 == 0, "grid_slot assumes wave64 and an even number of points per lane");
+
+// One wave's entry of a grid's chunk table: (min, max) of the centred grid over chunk c (its points below N).  The body
+// of the lone context's kernel (objective.hip) and of the batch's (batch.hip).
+__device__ inline void chunk_minmax_wave(const double *wc, int64_t N, int64_t c, int lane, double2 *out)
+{
+    double lo = INFINITY, hi = -INFINITY;
+    for (int q = 0; q < kPointsPerLane; ++q) {
+        const int64_t j = c * kChunk + q * kWave + lane;
+        if (j < N) {
+            const double x = wc[grid_slot(j)];
+            lo = fmin(lo, x);
+            hi = fmax(hi, x);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, off, kWave));
+        hi = fmax(hi, __shfl_down(hi, off, kWave));
+    }
+    if (lane == 0) out[c] = make_double2(lo, hi);
+}
 
 // Per-(particle, peak) constants staged in LDS: see objective.hip.
 struct PeakLor {

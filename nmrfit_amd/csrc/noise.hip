@@ -4,7 +4,7 @@
 // the batched fit rates it is not small next to the fits.  The deviates are a pure function of (seed, grid point): one
 // Philox4x32-10 block per point (the swarm's generator, pso_update.h, under a counter tag of its own) and one Box-Muller
 // pair for the two channels, so a replica is the same bits alone, in any batch, out of place (nmrfit_noise_replicas) or
-// in place on a batch's resident planes (nmrfit_batch_add_noise, batch.hip).  fp64 libdevice log / sin / cos, no fast
+// in place on a batch's resident planes (nmrfit_batch_add_noise, batch_data.hip).  fp64 libdevice log / sin / cos, no fast
 // forms; a thread per point, no atomics, no scratch, no LDS.
 #include "host_call.h"
 #include "nmrfit_amd_noise.h"

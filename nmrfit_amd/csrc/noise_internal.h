@@ -1,4 +1,4 @@
-// noise_internal.h -- shared by noise.hip (the kernels, nmrfit_noise_replicas) and batch.hip (nmrfit_batch_add_noise,
+// noise_internal.h -- shared by noise.hip (the kernels, nmrfit_noise_replicas) and batch_data.hip (nmrfit_batch_add_noise,
 // nmrfit_batch_spectrum): one spectrum of a noise launch, the argument check and the launches.
 #pragma once
 #include "nmrfit_internal.h"

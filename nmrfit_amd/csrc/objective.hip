@@ -23,7 +23,6 @@ __global__ void finalize_kernel(const double *__restrict__ partial, int64_t S, i
     f[i] = finalize_value(partial + i * n_chunks * (fit_im ? 2 : 1), n_chunks, N, fit_im);
 }
 
-// per-chunk (min, max) of the centred grid: one wave per chunk
 // residual rows of both channels (launch_objective, rows_fit_im): the two RMSEs of every row from the same per-block
 // sums in the same order -- 0.5 * (f2[2 i] + f2[2 i + 1]) is what finalize_kernel gives
 __global__ void finalize_rows_im_kernel(const double *__restrict__ partial, int64_t S, int64_t n_blocks, int64_t N,
@@ -41,26 +40,12 @@ __global__ void finalize_rows_im_kernel(const double *__restrict__ partial, int6
     f2[2 * i + 1] = sqrt(si / (double)N);
 }
 
+// per-chunk (min, max) of the centred grid: one wave per chunk
 __global__ void chunk_minmax_kernel(const double *__restrict__ wc, int64_t N, int64_t n_chunks,
                                     double2 *__restrict__ out)
 {
-    const int lane = threadIdx.x & (kWave - 1);
     const int64_t c = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
-    if (c >= n_chunks) return;
-    double lo = INFINITY, hi = -INFINITY;
-    for (int q = 0; q < kPointsPerLane; ++q) {
-        const int64_t j = c * kChunk + q * kWave + lane;
-        if (j < N) {
-            const double x = wc[grid_slot(j)];
-            lo = fmin(lo, x);
-            hi = fmax(hi, x);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fmin(lo, __shfl_down(lo, off, kWave));
-        hi = fmax(hi, __shfl_down(hi, off, kWave));
-    }
-    if (lane == 0) out[c] = make_double2(lo, hi);
+    if (c < n_chunks) chunk_minmax_wave(wc, N, c, threadIdx.x & (kWave - 1), out);
 }
 
 __global__ void centre_kernel(const double *__restrict__ w, int64_t N, double w0, double *__restrict__ wc)
@@ -175,10 +160,9 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     if (ctx->target_waves > 0) target_waves = ctx->target_waves;
     // Blocks: the unit of the canonical summation / phase re-seeding, a function of N only
     // (at most 16 per grid), so that results do not depend on S or on sharding.
-    const int64_t n_chunks = (N + kChunk - 1) / kChunk;
-    const int blk_chunks = (int)((n_chunks + kMaxBlocks - 1) / kMaxBlocks);
-    const int64_t n_blocks = (n_chunks + blk_chunks - 1) / blk_chunks;
-    const int64_t blk_len = (int64_t)blk_chunks * kChunk;
+    const BlockPlan bp = block_plan(N);
+    const int64_t n_chunks = bp.n_chunks, n_blocks = bp.n_blocks, blk_len = bp.blk_len;
+    const int blk_chunks = bp.blk_chunks;
     int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(n_blocks, (target_waves + S - 1) / S));
     static const bool seg_rule_r4 = [] {
         const char *e = getenv("NMRFIT_SEG_RULE");   // A/B knob: 3 = the round-3 rule (~16 tasks per SIMD)

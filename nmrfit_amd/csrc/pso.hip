@@ -667,9 +667,7 @@ int nmrfit_pso_create(nmrfit_ctx *ctx, int64_t S_local, int64_t S_global, int64_
     // personal-best step finds fp from p without another pointer argument, objective.hip).
     {
         const size_t nposts = (size_t)kSelectMaxPosts;
-        // (fg, best_f, g[D], best_x[D] | generations, stop code): two copies, 256-byte aligned, the flags right behind
-        // the doubles -- the deferred fold of a fused launch reads one and writes the other (PsoFused::flip)
-        const size_t state_bytes = (((size_t)(2 + 2 * D) * sizeof(double) + 2 * sizeof(long long)) + 255) & ~(size_t)255;
+        const size_t state_bytes = swarm_state_bytes(D);   // (two copies: host_call.h)
         const size_t p_bytes = (size_t)std::max<int64_t>(S_local * D, 0) * sizeof(double) + s1;   // p[S x D], fp[S]
         Carver c;
         const size_t o_lb = c.take((size_t)D * sizeof(double)), o_ub = c.take((size_t)D * sizeof(double));

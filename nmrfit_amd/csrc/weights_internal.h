@@ -1,4 +1,4 @@
-// weights_internal.h -- shared by weights.hip (the kernels, nmrfit_weights_build) and batch.hip
+// weights_internal.h -- shared by weights.hip (the kernels, nmrfit_weights_build) and batch_create.hip
 // (nmrfit_batch_create_regions): the layout of a ragged batch of weight regions and the two launches that turn it into
 // the spectra's error weights.
 #pragma once

@@ -325,7 +325,7 @@ class FitUtility:
         return plan
 
     def _batch_key(self, plan):
-        """The key under which core.fit_many may put this fit into a device batch with others (csrc/batch.hip: equal
+        """The key under which core.fit_many may put this fit into a device batch with others (csrc/batch_create.hip: equal
         kernel variant, imaginary-channel mode, maxiter and check_every; grid lengths, peak counts and swarm sizes may
         differ) -- or None when it must run on its own."""
         opt = self.options

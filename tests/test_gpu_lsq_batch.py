@@ -108,8 +108,11 @@ def _batch(specs, order, **kw):
                     [specs[k]["upper"] for k in order], swarmsize=8, seeds=list(range(1, len(order) + 1)), **kw)
 
 
-@pytest.mark.parametrize("order", [(0, 1, 2), (2, 0, 1)])
+@pytest.mark.parametrize("order", [(0, 1, 2), (2, 0, 1), (0, 1, 2, 0, 1, 2, 1)])
 def test_ragged_batch_equals_lone_contexts_bit_for_bit(ragged, order, monkeypatch):
+    """Seven fits are two parts of 3 + 4 (a batch splits from K = 6): the call walks per-part offsets into every array, the
+    part boundary lies between fits that differ in N and P, and the fits recur, so that a wrong offset lands on another
+    fit's block of another size."""
     specs, X, lone = ragged
     with _batch(specs, order) as fb:
         got = fb.normal_equations([X[k] for k in order])

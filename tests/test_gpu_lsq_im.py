@@ -1,5 +1,5 @@
 """
-GPU tier of least squares on both channels (include/nmrfit_amd_lsq_im.h; csrc/objective_rows_im.hip, lsq.hip, batch.hip).
+GPU tier of least squares on both channels (include/nmrfit_amd_lsq_im.h; csrc/objective_rows_im.hip, lsq.hip, batch_lsq.hip).
 
 Rows: the real rows and rho_re of the new call against nmrfit_residual_batch bit for bit, (rho_re + rho_im)/2 against
 nmrfit_objective_batch, rho_im against the RMS of the returned imaginary rows, and the imaginary rows point by point
@@ -279,11 +279,13 @@ def _raw_batch_call(fb, X):
 
 
 @pytest.mark.parametrize("mode", M.MODES)
-@pytest.mark.parametrize("order", [(0,), (0, 1, 2), (0, 2, 1)])
+@pytest.mark.parametrize("order", [(0,), (0, 1, 2), (0, 2, 1), (0, 1, 2, 0, 1, 2, 1)])
 def test_batch_equals_lone_contexts_bit_for_bit(ragged, order, mode, monkeypatch):
     """K = 1 and K = 3, ragged in N and P.  Under a workspace budget of 1 MiB the order (0, 2, 1) makes every fit a group of
     its own (fit 2's doubled rows alone exceed it; fits 0 and 1 are not neighbours), the order (0, 1, 2) groups fits 0
-    and 1: not a bit changes either way.  The swarms are untouched by the calls."""
+    and 1: not a bit changes either way.  The swarms are untouched by the calls.  K = 7 is two parts of 3 + 4 (a batch
+    splits from K = 6): the call walks per-part offsets into every array, doubled for the two channels; the part boundary
+    lies between fits that differ in N and P, and the fits recur, so that a wrong offset lands on another fit's block."""
     specs, X, lone = ragged
     with _batch(specs, order, mode) as fb:
         fb.run(3, 1)
