@@ -1,6 +1,6 @@
 // host_call.h -- what the host side of an entry point is built from besides nmrfit_internal.h's use_device and
-// NMRFIT_HIP: the device buffers and the stream of one call, the layout of an object's one allocation, and the HIP call
-// of a create function.  Host code only.
+// NMRFIT_HIP (host_call.hip): the argument checks of the calls on a context, the device buffers and the stream of one
+// call, the layout of an object's one allocation, and the HIP call of a create function.  Host code only.
 #pragma once
 #include "nmrfit_internal.h"
 
@@ -26,6 +26,33 @@ inline int refuse(int code, const std::string &msg)
 {
     set_error(msg);
     return code;
+}
+
+// What the entry points on a context (ctx.hip, ctx_eval.hip) begin with: the context is there, and its device is the
+// calling thread's current one
+inline int bind(const nmrfit_ctx *ctx)
+{
+    if (!ctx) return refuse(NMRFIT_E_INVALID, "null context");
+    NMRFIT_HIP(hipSetDevice(ctx->device));
+    return NMRFIT_OK;
+}
+
+// S parameter rows of P peaks at X, results at `out`
+inline int check_batch(int64_t S, int32_t P, const void *X, const void *out)
+{
+    if (S < 0 || P < 0) return refuse(NMRFIT_E_INVALID, "negative batch size or peak count");
+    if (P > kMaxPeaks)
+        return refuse(NMRFIT_E_INVALID, "P exceeds the supported maximum of " + std::to_string(kMaxPeaks) +
+                                            " peaks (per-peak records of a workgroup live in a CU's 160 KiB of LDS)");
+    if (S > 0 && (!X || !out)) return refuse(NMRFIT_E_INVALID, "null parameter/output pointer");
+    return NMRFIT_OK;
+}
+
+inline int check_fit_im(int fit_im)
+{
+    if (fit_im < 0 || fit_im > NMRFIT_FIT_IM_SUM)
+        return refuse(NMRFIT_E_INVALID, "fit_im must be 0 (real part), 1 (reference fit_im=True) or 2 (all-peak imaginary model)");
+    return NMRFIT_OK;
 }
 
 inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }

@@ -1,4 +1,4 @@
-// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), cabi.hip (nmrfit_jacobian) and
+// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), ctx_eval.hip (nmrfit_jacobian*) and
 // batch_lsq.hip (nmrfit_batch_normal_equations*): the per-fit records the kernels read and the launches.
 #pragma once
 #include "nmrfit_amd_lsq.h"

@@ -95,22 +95,22 @@ struct PeakWin {
     float hi;     // (f32, rounded outwards: 8 B per peak keep three workgroups per CU at P = 24)
 };
 
-void set_error(const std::string &msg);
-void analyse_grid(const double *w, int64_t N, double *w0, double *wspan, double *lane_step, double *grid_dev);   // cabi.hip
+void set_error(const std::string &msg);                  // host_call.hip: the calling thread's nmrfit_last_error()
+void analyse_grid(const double *w, int64_t N, double *w0, double *wspan, double *lane_step, double *grid_dev);   // ctx.hip
 struct DeviceInfo {
     bool known = false;
     int cus = 0;
     char arch[64] = {0};
 };
-int device_info_cached(int device, DeviceInfo *out);      // cabi.hip: compute units and arch name, once per process
-// cabi.hip: the device check of every entry point that takes a device index (a device is visible, the index is in range,
+int device_info_cached(int device, DeviceInfo *out);      // host_call.hip: compute units and arch name, once per process
+// host_call.hip: the device check of every entry point that takes a device index (a device is visible, the index is in range,
 // it is a gfx950), which also makes it the calling thread's current device
 int use_device(int device, DeviceInfo *info = nullptr);
-int check_spectra_count(const char *who, int32_t S);      // cabi.hip: 1..65535 spectra per call (a launch's grid.y / grid.x)
-hipError_t take_stream(int device, hipStream_t *out);     // cabi.hip: a recycled (or new) non-blocking stream
+int check_spectra_count(const char *who, int32_t S);      // host_call.hip: 1..65535 spectra per call (a launch's grid.y / grid.x)
+hipError_t take_stream(int device, hipStream_t *out);     // host_call.hip: a recycled (or new) non-blocking stream
 void give_stream(int device, hipStream_t s);              // ... handed back idle (synchronised)
-int hip_fail(hipError_t e, const char *what, const char *file, int line);
-// cabi.hip: device -> pageable host memory through the process's pinned double buffer (synchronous; stream-ordered after
+int hip_fail(hipError_t e, const char *what, const char *file, int line);   // host_call.hip
+// host_call.hip: device -> pageable host memory through the process's pinned double buffer (synchronous; stream-ordered after
 // what is queued on `st`)
 int staged_d2h(int device, hipStream_t st, void *dst_host, const void *src_dev, size_t bytes);
 
@@ -193,7 +193,7 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
 // imaginary rows second, and df [S][2] receives the two RMSEs of every row.  DEFAULT kernel only: a context set to
 // another variant, or so many peaks that DEFAULT's LDS records do not fit, is NMRFIT_E_UNSUPPORTED.  Every other residual
 // launch sees the real channel alone, whatever the context's fit_im.
-int ensure(nmrfit_ctx *ctx, double **buf, int64_t *cap, int64_t need);
+int ensure(nmrfit_ctx *ctx, double **buf, int64_t *cap, int64_t need);   // ctx.hip
 // centred grid + per-chunk (min,max) table from the raw device copy of w
 int prepare_grid(nmrfit_ctx *ctx, const double *d_w_raw);
 // d_dst[grid_slot(j)] = d_src[j], j < N (d_dst: n_chunks * kChunk doubles, padding untouched)

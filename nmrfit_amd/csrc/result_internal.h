@@ -1,5 +1,5 @@
 // result_internal.h -- the post-fit reconstruction (FitUtility.generate_result, nmrfit/utils.py:226-295) as one kernel
-// over a table of jobs: shared by cabi.hip (one fit: nmrfit_contributions, nmrfit_generate_result) and batch_data.hip (every
+// over a table of jobs: shared by ctx_eval.hip (one fit: nmrfit_contributions, nmrfit_generate_result) and batch_data.hip (every
 // fit of a device batch in one launch: nmrfit_batch_contributions).
 #pragma once
 #include "nmrfit_internal.h"

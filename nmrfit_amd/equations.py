@@ -167,28 +167,36 @@ class Evaluator:
                                                     _cabi.ptr(f)))
         return (R, f) if return_f else R
 
+    def _jacobian(self, who, both, fit_im, rows, c, s, J, r, normal):
+        """``jacobian`` and ``jacobian_im`` (``both``): the same call, without or with a leading channel axis."""
+        rows, P = self._as_batch(rows)
+        D = rows.shape[1]
+        c = _cabi.f64(c)
+        if rows.shape[0] != D + 1 or c.shape != (D,):
+            raise ValueError(who + ": rows must be (D + 1) x D and c have D entries")
+        ch = (2,) if both else ()
+        f = np.empty(ch or 1)
+        out = {"f2" if both else "f": f}
+        if J:
+            out["J"] = np.empty(ch + (self.N, D))
+        if r:
+            out["r"] = np.empty(ch + (self.N,))
+        if normal:
+            out["A"], out["g"] = np.empty(ch + (D, D)), np.empty(ch + (D,))
+        mode = (fit_im_mode(fit_im),) if both else ()
+        args = (self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s)) + mode + tuple(
+            _cabi.ptr(out.get(k)) for k in ("J", "r", "A", "g")) + (_cabi.ptr(f),)
+        _cabi.check(getattr(self._lib, "nmrfit_" + who)(*args))
+        if not both:
+            out["f"] = float(f[0])
+        return out
+
     def jacobian(self, rows, c, s, J=False, r=False, normal=False):
         """``nmrfit_jacobian`` (include/nmrfit_amd_lsq.h): the D + 1 residual rows of the parameter rows ``rows`` stay on
         the device; returns a dict with what was asked for -- ``J`` [N, D] = (R[i + 1] - R[0]) * c_i (row-major, the
         layout scipy takes), ``r`` [N] = R[0] * s, ``A`` [D, D] = J^T J and ``g`` [D] = J^T r (``normal``) -- and ``f``,
         the objective value of row 0."""
-        rows, P = self._as_batch(rows)
-        D = rows.shape[1]
-        c = _cabi.f64(c)
-        if rows.shape[0] != D + 1 or c.shape != (D,):
-            raise ValueError("jacobian: rows must be (D + 1) x D and c have D entries")
-        out = dict(f=np.empty(1))
-        if J:
-            out["J"] = np.empty((self.N, D))
-        if r:
-            out["r"] = np.empty(self.N)
-        if normal:
-            out["A"], out["g"] = np.empty((D, D)), np.empty(D)
-        _cabi.check(self._lib.nmrfit_jacobian(self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s), _cabi.ptr(out.get("J")),
-                                              _cabi.ptr(out.get("r")), _cabi.ptr(out.get("A")), _cabi.ptr(out.get("g")),
-                                              _cabi.ptr(out["f"])))
-        out["f"] = float(out["f"][0])
-        return out
+        return self._jacobian("jacobian", False, None, rows, c, s, J, r, normal)
 
     # -- both channels (include/nmrfit_amd_lsq_im.h) -------------------------------------------
     def residual_batch_im(self, X, fit_im):
@@ -206,22 +214,7 @@ class Evaluator:
         """``nmrfit_jacobian_im``: ``jacobian`` per channel.  Returns a dict with what was asked for, every array with a
         leading channel index (0 real, 1 imaginary) -- ``J`` [2, N, D], ``r`` [2, N], ``A`` [2, D, D], ``g`` [2, D]
         (``normal``) -- and ``f2`` [2] = (rho_re, rho_im) of row 0."""
-        rows, P = self._as_batch(rows)
-        D = rows.shape[1]
-        c = _cabi.f64(c)
-        if rows.shape[0] != D + 1 or c.shape != (D,):
-            raise ValueError("jacobian_im: rows must be (D + 1) x D and c have D entries")
-        out = dict(f2=np.empty(2))
-        if J:
-            out["J"] = np.empty((2, self.N, D))
-        if r:
-            out["r"] = np.empty((2, self.N))
-        if normal:
-            out["A"], out["g"] = np.empty((2, D, D)), np.empty((2, D))
-        _cabi.check(self._lib.nmrfit_jacobian_im(self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s), fit_im_mode(fit_im),
-                                                 _cabi.ptr(out.get("J")), _cabi.ptr(out.get("r")), _cabi.ptr(out.get("A")),
-                                                 _cabi.ptr(out.get("g")), _cabi.ptr(out["f2"])))
-        return out
+        return self._jacobian("jacobian_im", True, fit_im, rows, c, s, J, r, normal)
 
     # -- device-resident helpers (bench / swarm) ------------------------------------------
     def dev_alloc(self, nbytes):

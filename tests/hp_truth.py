@@ -70,7 +70,7 @@ def dawson(x):
 
 
 def grid_frame(w):
-    """(w0, wspan) of a grid exactly as the library forms them at context creation (csrc/cabi.hip analyse_grid)."""
+    """(w0, wspan) of a grid exactly as the library forms them at context creation (csrc/ctx.hip analyse_grid)."""
     w = np.asarray(w, dtype=np.float64)
     w0 = float(w[w.size // 2])
     return w0, float(np.max(np.abs(w - w0)))

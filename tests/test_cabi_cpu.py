@@ -145,6 +145,45 @@ def test_batch_argument_validation_needs_no_gpu():
         assert ei.value.code == _cabi.E_NO_DEVICE
 
 
+_CTX_PREFIXES = ("nmrfit_ctx_", "nmrfit_objective_", "nmrfit_residual_", "nmrfit_jacobian", "nmrfit_contributions",
+                 "nmrfit_generate_result", "nmrfit_dev_", "nmrfit_memcpy_", "nmrfit_timer_", "nmrfit_prof_", "nmrfit_last_launch")
+
+
+def test_every_entry_point_on_a_context_refuses_a_null_context():
+    """Every call that takes a context (but create and destroy, above) returns NMRFIT_E_INVALID for a null one, with its
+    other arguments valid-looking, before it touches a device: no GPU is needed, and none is opened where there is one."""
+    L = _cabi.lib()
+    tables = (_cabi.SIGNATURES, _cabi.DIAG_SIGNATURES, _cabi.LSQ_SIGNATURES, _cabi.LSQ_IM_SIGNATURES)
+    names = sorted(n for t in tables for n in t if n.startswith(_CTX_PREFIXES) and n not in ("nmrfit_ctx_create", "nmrfit_ctx_destroy"))
+    assert len(names) == 26, names
+    P, B, N = 1, 8, 16
+    D = 4 + 3 * P
+    X, c, buf = np.full((B, D), 0.5), np.ones(D), np.zeros(2 * B * N)
+    i64, i32, dbl, vp = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double(), ctypes.c_void_p()
+    p, ref = _cabi.ptr, ctypes.byref
+    calls = {
+        "nmrfit_ctx_set_weights": (p(buf),), "nmrfit_ctx_synchronize": (), "nmrfit_ctx_set_variant": (0,),
+        "nmrfit_ctx_set_fit_im": (0,), "nmrfit_ctx_set_stream": (None,), "nmrfit_ctx_n": (ref(i64),),
+        "nmrfit_objective_batch": (B, P, p(X), 0, p(buf)), "nmrfit_residual_batch": (B, P, p(X), p(buf), None),
+        "nmrfit_objective_batch_dev": (B, P, p(X), p(buf)), "nmrfit_residual_batch_dev": (B, P, p(X), p(buf), None),
+        "nmrfit_residual_batch_im": (B, P, p(X), 1, p(buf), None),
+        "nmrfit_contributions": (P, p(X), N, None, p(buf), p(buf)),
+        "nmrfit_generate_result": (P, p(X), N, None, p(buf), p(buf), p(buf), p(buf)),
+        "nmrfit_jacobian": (P, p(X), p(c), 1.0, None, None, None, None, p(buf)),
+        "nmrfit_jacobian_im": (P, p(X), p(c), 1.0, 1, None, None, None, None, p(buf)),
+        "nmrfit_dev_alloc": (64, ref(vp)), "nmrfit_dev_free": (p(buf),),
+        "nmrfit_memcpy_h2d": (p(buf), p(X), 64), "nmrfit_memcpy_d2h": (p(buf), p(X), 64),
+        "nmrfit_timer_begin": (), "nmrfit_timer_end": (ref(dbl),),
+        "nmrfit_prof_enable": (4,), "nmrfit_prof_mark": (), "nmrfit_prof_read": (p(buf), 4, ref(i64), p(X), 4, ref(i64), ref(dbl)),
+        "nmrfit_last_launch": (ref(i64), ref(i32), ref(i64)), "nmrfit_last_launch_workgroup": (ref(i32),),
+    }
+    assert sorted(calls) == names
+    for name in names:
+        assert getattr(L, name)(None, *calls[name]) == _cabi.E_INVALID, name
+        assert L.nmrfit_last_error(), name
+    assert not vp.value and not buf.any()
+
+
 def test_every_device_entry_point_reports_a_bad_device_index_alike():
     """The eight entry points that take a device index share one device check: with arguments that are otherwise valid and
     an index no machine has, each returns NMRFIT_E_NO_DEVICE with the same message -- that no device is visible (or, on

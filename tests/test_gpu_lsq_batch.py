@@ -85,6 +85,28 @@ def test_jacobian_beyond_the_normal_equations_limit():
         np.testing.assert_array_equal(m.jac(x), out["J"])             # the context is usable after the refusal
 
 
+def test_jacobian_through_three_staging_chunks():
+    """N = 16384, P = 24: J is 9.96 MB per channel, three 4 MiB chunks of the staged copy to host memory -- the smallest
+    size at which a pinned buffer is used a second time -- and the second channel's J lands behind the first's."""
+    from nmrfit_amd.equations import Evaluator
+    N = 16384
+    sp = _spectrum(N, 24)
+    s = 1.0 / np.sqrt(N)
+    with Evaluator(*S.spectrum_tuple(sp)) as ev:
+        rows, h = lsq.ResidualModel(ev, sp["lower"], sp["upper"]).rows(_interior(sp))
+        c = s / h
+        assert N * len(c) * 8 > 2 * (4 << 20)
+        R = ev.residual_batch(rows)
+        J = ev.jacobian(rows, c, s, J=True)["J"]
+        np.testing.assert_array_equal(J, ((R[1:] - R[0]) * c[:, None]).T)
+        R_re, R_im, _ = ev.residual_batch_im(rows, True)
+        J2 = ev.jacobian_im(rows, c, s, True, J=True)["J"]
+        assert J2.shape == (2, N, len(c))
+        np.testing.assert_array_equal(J2[0], ((R_re[1:] - R_re[0]) * c[:, None]).T)
+        np.testing.assert_array_equal(J2[1], ((R_im[1:] - R_im[0]) * c[:, None]).T)
+        np.testing.assert_array_equal(J2[0], J)
+
+
 RAGGED = [(512, 1), (700, 2), (4096, 24)]
 
 
@@ -219,6 +241,34 @@ def test_argument_validation(ragged):
             assert text in L.nmrfit_last_error()
         A2, g2, f2 = m.normal_equations(x)                             # after the refused calls a normal one succeeds
         np.testing.assert_array_equal(A2, lone[0][0])
+        # nmrfit_residual_batch: the refusals nmrfit_residual_batch_im is held to (test_gpu_lsq_im.py)
+        R0 = ev.residual_batch(rows)
+        pr, pR = _cabi.ptr(rows), _cabi.ptr(np.empty_like(R0))
+        for args, text in (((ev.handle, D + 1, 1, None, pR), b"null parameter/output pointer"),
+                           ((ev.handle, D + 1, 1, pr, None), b"null parameter/output pointer"),
+                           ((ev.handle, D + 1, -1, pr, pR), b"negative"), ((ev.handle, -1, 1, pr, pR), b"negative")):
+            assert L.nmrfit_residual_batch(*args, None) == _cabi.E_INVALID, args
+            assert text in L.nmrfit_last_error()
+        np.testing.assert_array_equal(ev.residual_batch(rows), R0)
+        # the two copies: a negative size, a null pointer with a positive size, each under its own name
+        host = np.arange(8.0)
+        dptr = ev.dev_alloc(host.nbytes)
+        for fn, name in ((L.nmrfit_memcpy_h2d, b"nmrfit_memcpy_h2d"), (L.nmrfit_memcpy_d2h, b"nmrfit_memcpy_d2h")):
+            dst, src = (dptr, _cabi.ptr(host)) if fn is L.nmrfit_memcpy_h2d else (_cabi.ptr(host), dptr)
+            for args in ((dst, src, -1), (None, src, 8), (dst, None, 8)):
+                assert fn(ev.handle, *args) == _cabi.E_INVALID, (name, args)
+                assert L.nmrfit_last_error() == b"bad arguments to " + name
+        ev.upload(dptr, host)
+        np.testing.assert_array_equal(ev.download(dptr, host.shape), host)
+        ev.dev_free(dptr)
+        # a variant the library does not hold, and one that does not exist
+        if not _cabi.has_ab_variants():
+            assert L.nmrfit_ctx_set_variant(ev.handle, _cabi.VARIANT_QUAD) == _cabi.E_UNSUPPORTED
+            assert b"A/B form" in L.nmrfit_last_error()
+            np.testing.assert_array_equal(ev.residual_batch(rows), R0)
+        assert L.nmrfit_ctx_set_variant(ev.handle, -1) == _cabi.E_INVALID
+        assert b"bad context or variant" in L.nmrfit_last_error()
+        np.testing.assert_array_equal(ev.residual_batch(rows), R0)
     with _batch(specs, (0, 1, 2)) as fb:
         good = fb.normal_equations(X)
         rows = np.concatenate([lsq.forward_rows(x, q["lower"], q["upper"])[0].ravel() for x, q in zip(X, specs)])

@@ -293,7 +293,7 @@ def test_non_finite_parameters_do_not_crash(eq):
 def test_context_churn_does_not_leak(eq):
     """Contexts that come and go (one per fitted spectrum) while another stays: the library recycles a closed
     context's idle HIP stream for the next one on the device (a new stream costs ~4 ms at first use, a default fit
-    ~25 ms; csrc/cabi.hip) -- never a stream that a live context still owns."""
+    ~25 ms; csrc/host_call.hip) -- never a stream that a live context still owns."""
     sp = synth.make_spectrum(4096, 2, seed=81)
     X = synth.make_swarm(sp["lower"], sp["upper"], 8, seed=82)
     sp2 = synth.make_spectrum(3000, 5, seed=83)
