@@ -10,6 +10,14 @@ intervals and its |x| = 7 and 16 boundaries, the far-field switch rho = 0.1 rela
 needles narrower than a grid step, lines wider than the span, widths below the floor, r outside [0, 1], phases to 1e3.
 The swarm step and device batches are read the same way through their fx, the reconstruction point by point.
 
+What this file covers of the objective kernel, and what it does not: the probes sit at in-chunk positions 0, 1, 63, 64,
+76 and 511, i.e. rows 0, 1 and 7 of a lane's eight (a point is row * 64 + lane), in swarms of at most 25 particles (the
+launch that leaves per-block sums to finalize_kernel).  The features above include a negative width and negative
+amplitudes, which put every particle with 32 peaks or more, and most smaller ones, on the kernel's GENERAL forms: the
+Lorentzian group form and the point-by-point Gaussian.  The two-operation pair form and the Gaussian recurrence
+(objective_kernel.h fast_all / rec_all), rows 2 to 6, peak counts 0, 2 to 7 and 10 to 15, the other launch forms and
+the swarm / batch boxes that reach the recurrence are held to truth in tests/test_gpu_pointwise_forms.py.
+
 Each test prints its worst err/tol ratio.
 """
 import math
@@ -144,9 +152,16 @@ def variants_modes():
             yield var, mode
 
 
-def check_objective(ev, X, w, u, v, j, worst, chunk):
+REC_VARIANTS = (_cabi.VARIANT_DEFAULT, _cabi.VARIANT_FARFIELD, _cabi.VARIANT_FARFIELD32)   # objective_kernel.h kRec
+
+
+def check_objective(ev, X, w, u, v, j, worst, chunk, rec=None):
+    """``rec``: None, or (lane_step, grid_dev, mask) for a probe in a FULL chunk of a uniform grid -- particle s, where
+    mask[s] says that the Gaussian recurrence runs for it, is held to the bound with the recurrence's term by the
+    variants that have the recurrence, and to the plain bound by every other variant."""
     N = w.size
-    truths = [hp.point(x, w, u, v, j, chunk=chunk) for x in X]
+    truths = [hp.point(x, w, u, v, j, chunk=chunk, rec=rec[:2] if rec is not None and rec[2][s] else None)
+              for s, x in enumerate(X)]
     for var, mode in variants_modes():
         ev.set_variant(var)
         try:
@@ -156,7 +171,7 @@ def check_objective(ev, X, w, u, v, j, worst, chunk):
                 continue
             raise
         for s, t in enumerate(truths):
-            want, tol = hp.objective_probe(t, mode)
+            want, tol = hp.objective_probe(t if var in REC_VARIANTS else hp.plain_bounds(t), mode)
             if var == _cabi.VARIANT_FARFIELD32:
                 tol += t["far32"]
             worst.check(f[s] * math.sqrt(N), want, tol, (var, mode, j, X.shape[1], s))
@@ -229,17 +244,30 @@ def hostile_box(w, P, kind, seed):
         elif kind == "beyond":
             lo += [5 * h, w.max() + 0.01 * span, 0.5]
             up += [50 * h, w.max() + 0.5 * span, 1.5]
+        elif kind in ("fine", "fine_neg"):     # lines the Gaussian recurrence takes (|d| <= 128/90), 0 < r < 1
+            neg = kind == "fine_neg" and k == P // 2
+            lo += [90 * h, c - 0.05, -1.5 if neg else 0.5]
+            up += [300 * h, c + 0.05, -0.5 if neg else 1.5]
         else:
             lo += [2 * h, c - 0.05, 0.5]
             up += [40 * h, c + 0.05, 1.5]
+    if kind in ("fine", "fine_neg"):           # "fine": the pair form; "fine_neg": one amplitude negative, the general form
+        lo[2], up[2] = 0.2, 0.9
     return np.array(lo), np.array(up)
 
 
-def check_state(x, fx, w, u, v, j, mode, worst, tag, n=24):
+def check_state(x, fx, w, u, v, j, mode, worst, tag, n=24, rec=None, forms=None):
+    """``rec``: None, or (lane_step, grid_dev) when j lies in a full chunk and the kernel variant has the Gaussian
+    recurrence: a sampled row for which the mirror says it runs takes the recurrence's term.  ``forms``: the (pair form,
+    recurrence) class every sampled row must be in, by the mirror."""
     N = w.size
     idx = np.unique(np.linspace(0, x.shape[0] - 1, min(n, x.shape[0])).astype(int))
     for s in idx:
-        t = hp.point(x[s], w, u, v, j)
+        if rec is not None or forms is not None:
+            kf = hp.kernel_forms(x[s], w)
+            if forms is not None:
+                assert (kf["fast"], kf["rec"]) == tuple(forms), (tag, int(s), kf)
+        t = hp.point(x[s], w, u, v, j, rec=rec if rec is not None and kf["rec"] else None)
         want, tol = hp.objective_probe(t, mode)
         worst.check(fx[s] * math.sqrt(N), want, tol, tag + (int(s),))
 

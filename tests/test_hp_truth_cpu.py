@@ -1,7 +1,9 @@
 """
 CPU tier: the high-precision truth of tests/hp_truth.py, pinned to the reference's golden vectors and to scipy, the
 one-hot probe that turns an objective into a pointwise readout, and the power of the bound -- perturbations of the size
-a subtly wrong kernel would make are flagged, while plain float64 evaluations pass.
+a subtly wrong kernel would make are flagged, while plain float64 evaluations pass.  The Gaussian recurrence has a term
+of its own in the bound: a float64 restatement of it leaves the plain bound and stays inside that one, subtly wrong
+recurrences leave it too.  Last, the Python mirror of the kernel's two form predicates, on both sides of every clause.
 """
 import math
 import os
@@ -206,3 +208,236 @@ def test_width_floor_is_the_floor_width_line():
     lim = hp.T_CAP / (wspan + abs(loc - w0))
     old = float(synth._dispersion(w[j:j + 1], 1.0, 2.0 / lim, loc, a)[0]) * (2.0 / width) / lim
     assert _flagged(old, t, "If2", "tol_If")
+
+
+# ---- the Gaussian recurrence: its own term of the bound ------------------------------------------------------------------
+
+SQRT_LN2_OVER_PI = 0.46971863934982566689      # csrc/objective_math.h kSqrtLn2OverPi
+
+
+def _rec_emulation(w, width, loc, a, c, lane, c_rel=0.0, skip_step=None, drop_d2=False):
+    """csrc/objective_chunk.h gauss_add_rec restated line by line in float64 (numpy exp2: the best case) for one lane of
+    the full chunk c of a uniform grid: the eight values AG 2^-t_q^2 at points c*512 + q*64 + lane, r = 0.  The
+    keyword arguments make it subtly wrong: C off by c_rel, `ratio *= C` skipped at one step, d^2 dropped from the
+    first ratio's exponent."""
+    w0, wspan, lane_step, _ = hp.grid_analysis(w)
+    assert lane_step != 0.0
+    wc = w - w0
+    ihw = 2.0 / width
+    cc = -(loc - w0) * ihw
+    ag2 = 2.0 * a * ihw * SQRT_LN2_OVER_PI
+    d = lane_step * ihw
+    C = float(np.exp2(-2.0 * d * d)) * (1.0 + c_rel)
+    t0 = wc[c * hp.CHUNK + lane] * ihw + cc
+    g = ag2 * float(np.exp2(-(t0 * t0 + 1.0)))
+    ratio = float(np.exp2(-((t0 + t0) * d + (0.0 if drop_d2 else d * d))))
+    out = [g]
+    for q in range(1, hp.ROWS):
+        g *= ratio
+        out.append(g)
+        if q + 1 < hp.ROWS and q != skip_step:
+            ratio *= C
+    return out
+
+
+def _rec_cases():
+    for N in (1101, 4096):
+        for desc in (False, True):
+            w = np.linspace(4.0, 3.0, N) if desc else np.linspace(3.0, 4.0, N)
+            h = abs(w[1] - w[0])
+            n_full = N // hp.CHUNK
+            for c in sorted({0, n_full // 2, n_full - 1}):
+                for steps in (64, 80, 128, 300, 1000):
+                    for frac in (0.1, 0.37, 0.5, 0.93):
+                        loc = float(w[c * hp.CHUNK]) + (w[1] - w[0]) * frac * hp.CHUNK
+                        yield N, desc, w, c, steps * h, loc
+
+
+def _rec_ratios(w, width, loc, c, lanes, rows=range(hp.ROWS), **mut):
+    """(err / plain bound, err / bound with the recurrence term) at the given rows and lanes.  (r = 0, yoff = 0: the
+    value is the Gaussian alone, so the second bound is the first plus C eps |G| rec_term -- one truth per point.)"""
+    w0, _, lane_step, grid_dev = hp.grid_analysis(w)
+    z = np.zeros(w.size)
+    x = np.array([0.0, 0.0, 0.0, 0.0, width, loc, 1.3])
+    ihw = 2.0 / width
+    for lane in lanes:
+        got = _rec_emulation(w, width, loc, 1.3, c, lane, **mut)
+        w_row0 = float(w[c * hp.CHUNK + lane])
+        t0 = (w_row0 - loc) * ihw
+        dt0 = (abs(w_row0 - w0) + abs(loc - w0)) * abs(ihw) + abs(t0)
+        for q in rows:
+            j = c * hp.CHUNK + q * hp.WAVE + lane
+            plain = hp.point(x, w, z, z, j, imag=False)
+            new_tol = plain["tol_Vf"] + hp.C * hp.EPS * abs(plain["Vf"]) * hp.rec_term(q, t0, lane_step * ihw, dt0, ihw, grid_dev)
+            err = abs(got[q] - plain["Vf"])
+            yield q, lane, err / plain["tol_Vf"], err / new_tol
+
+
+def test_default_bound_is_unchanged_by_the_recurrence_argument(golden_dir):
+    """Without the argument every bound is bit for bit what hp_truth gave before it had a recurrence term
+    (tests/golden/hp_truth_plain_bounds.npz: recorded from that version, same case, same points)."""
+    w, u, v, x = _probe_case(N=1500)
+    g = np.load(os.path.join(golden_dir, "hp_truth_plain_bounds.npz"))
+    for i, j in enumerate(g["j"]):
+        t = hp.point(x, w, u, v, int(j), chunk=(-0.3, 0.2))
+        for k in g.files:
+            if k != "j":
+                np.testing.assert_array_equal(t[k], g[k][i], err_msg="%s at %d" % (k, j))
+    for j in (0, int(np.argmin(np.abs(w - x[5]))), 1499):           # (the second: at a peak, where G is not ~0)
+        a = hp.point(x, w, u, v, j)
+        c = hp.point(x, w, u, v, j, rec=hp.grid_analysis(w)[2:])
+        assert c["tol_V"] >= a["tol_V"] and c["tol_I2"] == a["tol_I2"] and c["Vf"] == a["Vf"]
+        assert (c["tol_V"] > a["tol_V"]) == (0 < j < 1499)
+        for k, plain in c["plain"].items():                           # (the plain bounds come along, bit for bit)
+            np.testing.assert_array_equal(plain, a[k])
+        assert hp.plain_bounds(c)["tol_V"] == a["tol_V"] and hp.plain_bounds(a) is a
+    # one Gaussian alone: the bound with the term is the plain one plus C eps |G| rec_term (what _rec_ratios uses)
+    w = np.linspace(3.0, 4.0, 4096)
+    z = np.zeros(w.size)
+    w0, _, lane_step, grid_dev = hp.grid_analysis(w)
+    x1 = np.array([0.0, 0.0, 0.0, 0.0, 0.03, 3.4, 1.3])
+    j, q = 1024 + 5 * 64 + 9, 5
+    a, c = hp.point(x1, w, z, z, j, imag=False), hp.point(x1, w, z, z, j, imag=False, rec=(lane_step, grid_dev))
+    ihw, w_row0 = 2.0 / 0.03, float(w[j - q * 64])
+    t0 = (w_row0 - 3.4) * ihw
+    add = hp.C * hp.EPS * abs(a["Vf"]) * hp.rec_term(q, t0, lane_step * ihw, (abs(w_row0 - w0) + abs(3.4 - w0)) * ihw + abs(t0),
+                                                      ihw, grid_dev)
+    assert c["tol_Vf"] == pytest.approx(a["tol_Vf"] + add, rel=1e-13) and add > a["tol_Vf"]
+
+
+def test_recurrence_emulation_within_new_bound_and_breaks_the_plain_one():
+    """The float64 restatement of the recurrence stays inside the bound with the recurrence term everywhere, and leaves
+    the plain Gaussian bound somewhere (rows far from the lane's first point, |t_q| ~ 0): why the term exists."""
+    worst_old, worst_new, where_old, where_new = 0.0, 0.0, None, None
+
+    def scan(tag, ratios):
+        nonlocal worst_old, worst_new, where_old, where_new
+        for q, lane, r_old, r_new in ratios:
+            if r_old > worst_old:
+                worst_old, where_old = r_old, tag + (q, lane)
+            if r_new > worst_new:
+                worst_new, where_new = r_new, tag + (q, lane)
+    for N, desc, w, c, width, loc in _rec_cases():
+        scan((N, desc, c, width, loc), _rec_ratios(w, width, loc, c, (0, 21, 42, 63)))
+    # where the plain bound is thinnest: row 7 of every lane, the centre inside that row, t0 ~ 11 half-widths away
+    w = np.linspace(3.0, 4.0, 4096)
+    h = w[1] - w[0]
+    for c in (2, 3, 4):
+        for frac in (0.9, 0.93, 0.96, 0.99):
+            loc = float(w[c * hp.CHUNK]) + h * frac * hp.CHUNK
+            scan((4096, False, c, 80 * h, loc), _rec_ratios(w, 80 * h, loc, c, range(hp.WAVE), rows=(7,)))
+    print("recurrence emulation: worst err/tol %.3g against the plain bound at %s" % (worst_old, where_old))
+    print("recurrence emulation: worst err/tol %.3g against the bound with the recurrence term at %s" % (worst_new, where_new))
+    assert worst_new < 1.0, (worst_new, where_new)
+    assert worst_old > 1.0, (worst_old, where_old)
+
+
+def _mutant_case():
+    N = 4096
+    w = np.linspace(3.0, 4.0, N)
+    h = w[1] - w[0]
+    c = 3
+    return w, 300 * h, float(w[c * hp.CHUNK]) + 0.93 * hp.CHUNK * h, c
+
+
+@pytest.mark.parametrize("mut", [dict(c_rel=1e-12), dict(c_rel=-1e-12), dict(skip_step=3), dict(drop_d2=True)],
+                         ids=["C_plus_1e-12", "C_minus_1e-12", "ratio_step_skipped", "d2_dropped"])
+def test_subtly_wrong_recurrence_is_flagged(mut):
+    """A relative error of 1e-12 in C = 2^(-2 d^2), one skipped `ratio *= C`, d^2 missing from the first ratio's
+    exponent: each leaves the bound with the recurrence term, at a row where the correct recurrence is inside."""
+    w, width, loc, c = _mutant_case()
+    lanes = (0, 31, 63)
+    good = max(r for *_, r in _rec_ratios(w, width, loc, c, lanes))
+    bad = max(r for *_, r in _rec_ratios(w, width, loc, c, lanes, **mut))
+    print("recurrence %s: worst err/tol %.3g (correct: %.3g)" % (mut, bad, good))
+    assert good < 1.0
+    assert bad > 1.0
+
+
+# ---- the mirror of the kernel's two form predicates ---------------------------------------------------------------------
+
+def _forms_grid(N=4096):
+    w = np.linspace(3.0, 4.0, N)
+    return w, w[1] - w[0]
+
+
+def _particle(r, peaks):
+    return np.concatenate([[0.1, 2.0, r, 1e-4], np.ravel(peaks)])
+
+
+def test_grid_analysis_mirrors_the_context():
+    w, h = _forms_grid(1024)
+    w0, wspan, lane_step, grid_dev = hp.grid_analysis(w)
+    assert (w0, wspan) == hp.grid_frame(w)
+    assert lane_step == pytest.approx(64 * h, rel=1e-12) and 0.0 <= grid_dev <= 4 * np.finfo(float).eps * 4.0
+    assert hp.grid_analysis(w[::-1].copy())[2] == pytest.approx(-64 * h, rel=1e-12)
+    assert hp.grid_analysis(np.linspace(3.0, 4.0, 1023))[2:] == (0.0, 0.0)          # fewer than two chunks
+    s = np.linspace(0.0, 1.0, 1101)
+    assert hp.grid_analysis(3.0 + s + 0.35 * s * s)[2:] == (0.0, 0.0)               # not uniform
+    bent = w.copy()
+    bent[500] += 2e-6 * h                                                            # beyond 1e-6 of a step
+    assert hp.grid_analysis(bent)[2] == 0.0
+    bent[500] = w[500] + 0.5e-6 * h
+    assert hp.grid_analysis(bent)[2] != 0.0 and hp.grid_analysis(bent)[3] >= 0.9e-6 * h
+
+
+def test_kernel_forms_pair_form_clauses():
+    w, h = _forms_grid()
+    peaks = [[100 * h, 3.1 + 0.05 * k, 1.0] for k in range(17)]
+    f = hp.kernel_forms(_particle(0.5, peaks), w)
+    assert f["fast"] and f["sign_ok"] and f["fast_margin"] > 50
+    flipped = [list(p) for p in peaks]
+    flipped[16][2] = -1.0                                                            # a sign flip in the last group
+    f = hp.kernel_forms(_particle(0.5, flipped), w)
+    assert not f["fast"] and not f["sign_ok"] and f["fast_margin"] == -math.inf
+    flipped[16][2], flipped[16][0] = 1.0, -100 * h                                   # ... by the width's sign
+    assert not hp.kernel_forms(_particle(0.5, flipped), w)["fast"]
+    assert not hp.kernel_forms(_particle(0.0, peaks), w)["fast"]                     # r = 0: al = 0
+    assert not hp.kernel_forms(_particle(-0.2, peaks), w)["fast"]
+    assert hp.kernel_forms(_particle(0.5, peaks[:0]), w)["fast"]                     # no peak: nothing refuses
+    # the exponent budget, by eight needles of one aligned group and not by sign
+    needle = [0.8e-5 * h, 3.5, 1.0]                                                  # 32 of the 250 each
+    assert hp.kernel_forms(_particle(0.5, [needle]), w)["ehi"] == 32
+    seven = [list(needle) for _ in range(7)] + peaks[:9]
+    eight = [list(needle) for _ in range(8)] + peaks[:8]
+    straddle = peaks[:4] + [list(needle) for _ in range(8)] + peaks[:4]              # four in each of two groups
+    f7, f8, fs = (hp.kernel_forms(_particle(0.5, p), w) for p in (seven, eight, straddle))
+    assert f8["sign_ok"] and not f8["fast"] and f8["fast_margin"] < 0 and f8["ehi"] >= hp.EXP_BUDGET
+    assert f7["fast"] and f7["fast_margin"] > 0 and f8["ehi"] - 32 < f7["ehi"] < hp.EXP_BUDGET
+    assert fs["fast"]
+    # ... and from below: amplitudes so large that the sum of ilogb(1/al) leaves -250
+    big = [[100 * h, 3.5, 1e9] for _ in range(8)]                                   # -34 each
+    f = hp.kernel_forms(_particle(0.5, big), w)
+    assert f["sign_ok"] and not f["fast"] and f["elo"] <= -hp.EXP_BUDGET
+    big[0][2] = 1.0
+    assert hp.kernel_forms(_particle(0.5, big), w)["fast"]
+    assert not hp.kernel_forms(_particle(0.5, [[100 * h, 3.5, 1e305]]), w)["fast"]   # al >= 1e300
+    f = hp.kernel_forms(_particle(1.0, [[100 * h, 3.5, 5e-324]]), w)                 # 0 < al, 1/al overflows
+    assert f["sign_ok"] and f["edge"]
+    assert not hp.kernel_forms(_particle(1.0, [[100 * h, 3.5, 1e-300]]), w)["edge"]
+
+
+def test_kernel_forms_recurrence_clauses():
+    w, h = _forms_grid()
+    lane_step = hp.grid_analysis(w)[2]
+    for r in (0.5, 0.0):                                                             # (independent of the pair form)
+        under = hp.kernel_forms(_particle(r, [[300 * h, 3.5, 1.0], [lane_step * (1 + 1e-9), 3.2, 1.0]]), w)
+        over = hp.kernel_forms(_particle(r, [[300 * h, 3.5, 1.0], [-lane_step * (1 - 1e-9), 3.2, 1.0]]), w)
+        assert under["rec"] and 0 < under["rec_margin"] < 1e-8 and under["d"] < 2.0
+        assert not over["rec"] and -1e-8 < over["rec_margin"] < 0 and over["d"] > 2.0
+        assert under["fast"] == (r == 0.5)
+    x = _particle(0.5, [[300 * h, 3.5, 1.0]])
+    assert hp.kernel_forms(x, w)["rec"] and hp.kernel_forms(x, w[::-1].copy())["rec"]
+    s = np.linspace(0.0, 1.0, w.size)
+    f = hp.kernel_forms(x, 3.0 + s + 0.35 * s * s)                                   # a non-uniform grid
+    assert not f["rec"] and f["rec_margin"] == -math.inf and f["fast"]
+    assert not hp.kernel_forms(x, np.linspace(3.0, 4.0, 1023))["rec"]                # N = 1023 against 1024
+    assert hp.kernel_forms(_particle(0.5, [[300.0 / 1023, 3.5, 1.0]]), np.linspace(3.0, 4.0, 1024))["rec"]
+    # the grid's departure from the line: |it| grid_dev 11e10 <= 1
+    bent = w.copy()
+    bent[500] += 0.5e-6 * h
+    dev = hp.grid_analysis(bent)[3]
+    wide, narrow = 2.0 * dev * hp.REC_DEVK * 1.01, 2.0 * dev * hp.REC_DEVK * 0.99
+    assert narrow > 64 * h                                                           # (|d| <= 2 holds for both)
+    assert hp.kernel_forms(_particle(0.5, [[wide, 3.5, 1.0]]), bent)["rec"]
+    assert not hp.kernel_forms(_particle(0.5, [[narrow, 3.5, 1.0]]), bent)["rec"]
