@@ -16,6 +16,8 @@ around it, behind the reference's own API for that path:
                                                                  DEVICE, all refits one batch -> ReplicaFits (area_fraction_std, ...)
     nmrfit_amd.fit_replicas_many(jobs, replicas=32)              the same for several spectra, packed into ragged batches
     nmrfit_amd.noise.replicas(us, vs, sigma_u, sigma_v, seeds)   the noisy copies alone (noise.normals / replicas_host: the numpy mirror)
+    nmrfit_amd.fit_many(jobs, quality=True)                      every fit carries fit.quality: residual statistics per peak region,
+                                                                 reduced on the DEVICE (residual_stats / residual_stats_many alone)
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
@@ -27,7 +29,8 @@ bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
-from . import batch, containers, equations, noise, peaks, proc_autophase, pso, synth, utils  # noqa: F401
+from . import batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, utils  # noqa: F401
+from .quality import FitQuality, residual_stats, residual_stats_many  # noqa: F401
 from .noise import fit_replicas, fit_replicas_many  # noqa: F401
 from .containers import Data, select_peaks_many, shift_phase_many  # noqa: F401
 

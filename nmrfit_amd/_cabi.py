@@ -177,6 +177,12 @@ NOISE_SIGNATURES = {
     "nmrfit_batch_add_noise": [_VP, _VP, _VP, _VP],
     "nmrfit_batch_spectrum": [_VP, _I32, _VP, _VP],
 }
+# QUALITY_SIGNATURES: include/nmrfit_amd_quality.h (residual statistics of finished fits reduced on the device, from host
+# arrays or on a batch's resident spectra)
+QUALITY_SIGNATURES = {
+    "nmrfit_quality_stats": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_quality_stats": [_VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                    # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -281,7 +287,7 @@ def lib():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
-                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()):
+                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -206,6 +206,35 @@ class FitBatch:
         _cabi.check(self._lib.nmrfit_batch_spectrum(self._h, k, _cabi.ptr(u), _cabi.ptr(v)))
         return u, v
 
+    # -- residual statistics (include/nmrfit_amd_quality.h) ----------------------------------------
+    def residual_stats(self, X=None, regions=None):
+        """Per fit its ``quality.FitQuality``: the residual V_fit - V_data reduced on the device over the batch's
+        resident spectra (csrc/quality.hip) -- per region, over the whole grid and over what no region holds -- in one
+        call for all K fits; (R_k + 2) rows of 8 doubles per fit come back.  ``X``: the K parameter vectors, allowed in
+        any state; None: every fit's best position (``NmrfitError`` with the state code before the first generation).
+        ``regions``: K lists of ``(lo, hi)`` in units of w; None: no regions.  Bit for bit
+        ``quality.residual_stats_host`` of the arrays ``generate()`` returns, and ``quality.residual_stats`` of the
+        spectrum alone.  The swarms are not touched."""
+        from . import quality
+        if regions is None:
+            regions = [None] * self.K
+        if len(regions) != self.K:
+            raise ValueError("FitBatch.residual_stats: one list of regions per fit")
+        R, edges = quality.pack_edges(regions)
+        x = None
+        if X is not None:
+            if len(X) != self.K:
+                raise ValueError("FitBatch.residual_stats: one parameter vector per fit")
+            X = [_cabi.f64(xk).ravel() for xk in X]
+            for k, xk in enumerate(X):
+                if xk.shape != (self.D[k],):
+                    raise ValueError("FitBatch.residual_stats: fit %d takes %d parameters" % (k, self.D[k]))
+            x = np.concatenate(X)
+        out = np.empty((int(R.sum()) + 2 * self.K) * quality.ROW)
+        _cabi.check(self._lib.nmrfit_batch_quality_stats(self._h, _cabi.ptr(x), _cabi.ptr(R),
+                                                         _cabi.ptr(edges) if edges.size else None, _cabi.ptr(out)))
+        return quality.split_rows(out, R, self.D)
+
     # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
     def normal_equations(self, X, channels="real"):
         """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``

@@ -36,7 +36,7 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
 
 
 def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
-             batch_polish=False, **kwargs):
+             batch_polish=False, quality=False, **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -92,11 +92,19 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       include/nmrfit_amd_lsq_im.h): the loop minimises the objective their swarms minimised, (rho_re + rho_im)/2, where
       the per-fit path refines the real channel and can only accept or reject against it.  ``error`` is that objective
       at the accepted point, never above the swarm's.  ``fit_im=False`` jobs behave as under ``True``; fits that end
-      up alone and batches with any D > 76 keep the per-fit path."""
+      up alone and batches with any D > 76 keep the per-fit path.
+    * ``quality=True``: every returned fit carries ``fit.quality`` (``nmrfit_amd.quality.FitQuality``): the residual
+      V_fit - V_data at its FINAL ``params`` reduced on the device per peak region (the peaks' bounds), over the whole
+      grid and over what no region holds -- (P + 2) rows of 64 bytes per fit instead of the arrays of ``generate`` --
+      bit for bit ``residual_stats(w, u, v, fit.params, bounds)``.  The fits of a device batch go through
+      ``FitBatch.residual_stats`` while the batch is resident (those with ``options['polish']`` are refined before
+      that, not after the batch has closed), the fits that ran alone through one ``residual_stats_many`` call per
+      device.  ``params`` and ``error`` do not change.  With ``shard=True`` the rows stay on the rank that made them,
+      like the arrays of ``generate``."""
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights),
-                 "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish))
+                 "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish), bool(quality))
     if devices is not None:
         if shard:
             raise ValueError("fit_many: shard=True divides the jobs over PROCESSES, devices=[...] over the GPUs of this "
@@ -125,6 +133,7 @@ class _Call(typing.NamedTuple):
     scale: object                # ``generate``: False (no reconstruction), or generate_result's scale (True -> 1)
     device_weights: bool
     batch_polish: object         # False, True (fit_im=False jobs), or "both" (the jobs of fit_im batches too, on both channels)
+    quality: bool = False        # every fit gets ``quality``: its residual statistics per peak region (quality.py)
 
 
 def _result_record(f):
@@ -239,6 +248,7 @@ class _Batch:
 
     def __init__(self, fb, fits, plans, key, idx):
         self.fb, self.fits, self.plans, self.key, self.idx = fb, fits, plans, key, idx
+        self.quality = None      # read(), ``call.quality``: the fits' FitQuality, made while the batch was resident
 
     @classmethod
     def create(cls, fits, plans, key, idx):
@@ -268,7 +278,9 @@ class _Batch:
         not False -- the reconstruction of every fit in one launch (FitBatch.generate).  ``call.batch_polish``: the fits
         with options['polish'] and fit_im=False are refined here, in lock step, from the batch's resident spectra
         (FitBatch.polish); their entries of ``best`` are then the refined ones and their indices come back as
-        ``refined``: store leaves them alone.  Closes the batch.  Returns (refined, status, best, results)."""
+        ``refined``: store leaves them alone.  ``call.quality``: the residual statistics of every fit at its final
+        parameters, from the resident spectra (FitBatch.residual_stats) -- the fits store would refine one by one are
+        refined here first and count as ``refined``.  Closes the batch.  Returns (refined, status, best, results)."""
         fits, fb, refined = self.fits, self.fb, set()
         polished = sum(1 for f in fits if f.options.get('polish', False))
         try:
@@ -286,18 +298,18 @@ class _Batch:
                     for k in which:
                         best[k] = new[k]
                     refined = set(which)
+            if call.quality:
+                refined |= self._refine_per_fit(call, refined, best)
+                self.quality = fb.residual_stats([x for x, _ in best], [_peak_regions(f) for f in fits])
         finally:
             fb.close()
         return refined, status, best, results
 
-    def store(self, call, refined, status, best, results):
-        """The batch's results into the FitUtility objects (what FitUtility.fit and generate_result leave behind).  Fits
-        with options['polish'] that read has not ``refined`` are refined first (FitUtility._polish, ``call.threads`` at a
-        time); every polished fit is reconstructed from its refined parameters."""
-        from .pso import STOP_MESSAGES
-        fits, plans, scale = self.fits, self.plans, call.scale
-        polished = [k for k, f in enumerate(fits) if f.options.get('polish', False)]
-        per_fit = [k for k in polished if k not in refined]
+    def _refine_per_fit(self, call, refined, best):
+        """FitUtility._polish, ``call.threads`` at a time, for the fits with options['polish'] that are not in
+        ``refined``: their entries of ``best`` become the refined ones.  Returns their indices."""
+        fits, plans = self.fits, self.plans
+        per_fit = [k for k, f in enumerate(fits) if f.options.get('polish', False) and k not in refined]
         if per_fit:
             def refine(k):
                 return fits[k]._polish(best[k][0], best[k][1], plans[k])
@@ -308,6 +320,16 @@ class _Batch:
                 new = [refine(k) for k in per_fit]
             for k, xf in zip(per_fit, new):
                 best[k] = xf
+        return set(per_fit)
+
+    def store(self, call, refined, status, best, results):
+        """The batch's results into the FitUtility objects (what FitUtility.fit and generate_result leave behind).  Fits
+        with options['polish'] that read has not ``refined`` are refined first (FitUtility._polish, ``call.threads`` at a
+        time); every polished fit is reconstructed from its refined parameters."""
+        from .pso import STOP_MESSAGES
+        fits, plans, scale = self.fits, self.plans, call.scale
+        polished = [k for k, f in enumerate(fits) if f.options.get('polish', False)]
+        self._refine_per_fit(call, refined, best)
         for k, (f, p, st, (x, fx)) in enumerate(zip(fits, plans, status, best)):
             # (pyswarm's closing line, once per fit like the plain loop prints it)
             if st["stop"]:
@@ -315,6 +337,8 @@ class _Batch:
             else:
                 print('Stopping search: maximum iterations reached --> {:}'.format(self.key.maxiter))
             f._finish(x, fx)
+            if self.quality is not None:
+                f.quality = self.quality[k]
             if k in polished:
                 if scale is not False:
                     f.generate_result(scale)      # (from the refined parameters: the batch's launch used the swarm's)
@@ -441,9 +465,15 @@ def _fit_many_local(jobs, call):
     return _fit_alone(fits, pipe.plans, [i for i in range(n) if i not in pipe.batched], call)
 
 
+def _peak_regions(f):
+    """The regions of a fit's residual statistics: its peaks' bounds."""
+    return [tuple(p.bounds) for p in f.data.peaks]
+
+
 def _fit_alone(fits, plans, alone, call):
     """The fits that ran in no batch, through fit() -- with the plan made for them, if any -- on ``call.threads``
-    threads; serially when any carries an ``exchange`` (a communicator serves one swarm at a time)."""
+    threads; serially when any carries an ``exchange`` (a communicator serves one swarm at a time).  ``call.quality``:
+    their residual statistics in one residual_stats_many call per device."""
     def lone(i):
         fits[i].fit(plan=plans.get(i))
         if call.scale is not False:
@@ -454,4 +484,14 @@ def _fit_alone(fits, plans, alone, call):
     else:
         with ThreadPoolExecutor(max_workers=int(call.threads)) as pool:
             list(pool.map(lone, alone))
+    if call.quality:
+        from . import quality
+        by_device = {}
+        for i in alone:
+            by_device.setdefault(fits[i]._device(), []).append(i)
+        for device, idx in by_device.items():
+            got = quality.residual_stats_many([(fits[i].data.w, fits[i].data.u, fits[i].data.v) for i in idx],
+                                              [fits[i].params for i in idx], [_peak_regions(fits[i]) for i in idx], device=device)
+            for i, q in zip(idx, got):
+                fits[i].quality = q
     return fits

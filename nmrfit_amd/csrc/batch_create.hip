@@ -225,6 +225,7 @@ int upload_and_prepare(BatchPart *b, const PartLayout &L, const std::vector<Batc
     b->d_bestx = reinterpret_cast<double *>(base + L.bestx);
     b->d_tables = reinterpret_cast<BatchFit *>(base + L.tables);
     double *d_raw = reinterpret_cast<double *>(base + L.raw);
+    b->d_w_plain = d_raw;   // (the w plane stays as uploaded: the region edges of the residual statistics are found on it)
     NMRFIT_HIP(hipMemcpyAsync(b->d_tables, tabs.data(), tabs.size() * sizeof(BatchFit), hipMemcpyHostToDevice, st));
     NMRFIT_HIP(hipMemcpyAsync(b->d_bestx + b->Dsum, b->boff.data(), (size_t)K * sizeof(int64_t), hipMemcpyHostToDevice, st));
     const size_t plane = Nsum * sizeof(double);
@@ -258,6 +259,7 @@ int part_destroy(BatchPart *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->d_result) (void)hipFree(b->d_result);
+    if (b->d_quality) (void)hipFree(b->d_quality);
     if (b->d_block) (void)hipFree(b->d_block);
     if (b->stream) give_stream(b->device, b->stream);
     delete b;

@@ -1,10 +1,12 @@
 // batch_data.hip -- what a device batch gives back and takes besides its swarms' results, all of it on the parts' resident
 // arrays: the post-fit reconstruction of every fit (nmrfit_batch_contributions: enqueued per part, then copied back part
-// after part), noise added in place to the resident spectra (nmrfit_batch_add_noise) and a fit's spectrum as the kernels
-// see it (nmrfit_batch_spectrum).  The kernels are result.hip's and noise.hip's.
+// after part), noise added in place to the resident spectra (nmrfit_batch_add_noise), a fit's spectrum as the kernels
+// see it (nmrfit_batch_spectrum) and the residual statistics of every fit (nmrfit_batch_quality_stats).  The kernels are
+// result.hip's, noise.hip's and quality.hip's.
 #include "batch_part.h"
 #include "nmrfit_amd_noise.h"
 #include "noise_internal.h"
+#include "quality_internal.h"
 #include "result_internal.h"
 
 #include <algorithm>
@@ -138,6 +140,87 @@ static int part_spectrum(BatchPart *b, int32_t k, double *u_out, double *v_out)
     return rc;
 }
 
+// include/nmrfit_amd_quality.h for the fits of a part: the three launches of quality.hip on the part's stream, over the
+// resident planes (grid_slot order) and, for the regions' nearest points, the grids as they were uploaded.  x: this
+// part's parameter vectors (host), or null: the best rows -- the part must have started, and a generation whose fold
+// still waits is folded first, as for the reconstruction.  R, edges: this part's shares, already checked.  *d_out: the
+// part's rows in device memory (n_rows of them); the caller copies and synchronises.  The launches' buffers are one
+// block that stays with the part (d_quality, grown on demand, freed with the part): a hipFree per call would wait for
+// whatever the other batches of a fit_many call have queued on the device.
+static int part_quality_enqueue(BatchPart *b, const double *x, const int32_t *R, const double *edges, double **d_out,
+                                int64_t *n_rows)
+{
+    int rc = x ? bind_batch(b) : bind_started(b, "nmrfit_batch_quality_stats");
+    if (rc != NMRFIT_OK) return rc;
+    if (!x && (rc = flush_fold(b)) != NMRFIT_OK) return rc;   // (the tail launch leaves every fit's best row in d_bestx)
+    const int32_t K = b->K;
+    std::vector<WeightSpec> specs;
+    std::vector<int32_t> region_spec;
+    weights_layout(K, b->Nk.data(), R, &specs, &region_spec);
+    int64_t rows = 0, n_partial = 0;
+    int32_t Rmax = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        rows += R[k] + 2;
+        n_partial += (int64_t)(R[k] + 2) * quality_tiles(b->Nk[(size_t)k]);
+        Rmax = std::max(Rmax, R[k]);
+    }
+    const size_t nr = region_spec.size();
+    Carver c;
+    const size_t o_jobs = c.take((size_t)K * sizeof(QualityJob)), o_specs = c.take(specs.size() * sizeof(WeightSpec));
+    const size_t o_rs = c.take(nr * sizeof(int32_t)), o_fl = c.take(2 * nr * sizeof(int64_t)), o_edges = c.take(2 * nr * sizeof(double));
+    const size_t o_partial = c.take((size_t)n_partial * kQualityRow * sizeof(double));
+    const size_t o_out = c.take((size_t)rows * kQualityRow * sizeof(double)), o_x = c.take(x ? (size_t)b->Dsum * sizeof(double) : 0);
+    if (b->cap_quality < c.total) {
+        if (b->d_quality) (void)hipFree(b->d_quality);
+        b->d_quality = nullptr;
+        b->cap_quality = 0;
+        NMRFIT_HIP(hipMalloc(&b->d_quality, c.total));
+        b->cap_quality = c.total;
+    }
+    unsigned char *base = reinterpret_cast<unsigned char *>(b->d_quality);
+    QualityJob *d_jobs = reinterpret_cast<QualityJob *>(base + o_jobs);
+    WeightSpec *d_specs = reinterpret_cast<WeightSpec *>(base + o_specs);
+    int32_t *d_rs = reinterpret_cast<int32_t *>(base + o_rs);
+    int64_t *d_fl = reinterpret_cast<int64_t *>(base + o_fl);
+    double *d_edges = reinterpret_cast<double *>(base + o_edges), *d_partial = reinterpret_cast<double *>(base + o_partial);
+    double *d_x = reinterpret_cast<double *>(base + o_x);
+    *d_out = reinterpret_cast<double *>(base + o_out);
+    std::vector<QualityJob> jobs((size_t)K);
+    int64_t at_row = 0, at_partial = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        const BatchFit &f = b->h_fits[(size_t)k];
+        QualityJob &j = jobs[(size_t)k];
+        j = QualityJob{};
+        j.w = f.wc;
+        j.u = f.u;
+        j.v = f.v;
+        j.x = (x ? d_x : b->d_bestx) + b->boff[(size_t)k];
+        j.first_last = d_fl + 2 * specs[(size_t)k].r_off;
+        j.partial = d_partial + at_partial * kQualityRow;
+        j.out = *d_out + at_row * kQualityRow;
+        j.w0 = f.w0;
+        j.wspan = f.wspan;
+        j.N = f.N;
+        j.P = f.P;
+        j.R = R[k];
+        j.tiles = (int32_t)quality_tiles(f.N);
+        j.slotted = 1;
+        at_row += R[k] + 2;
+        at_partial += (int64_t)(R[k] + 2) * j.tiles;
+    }
+    hipStream_t st = b->stream;
+    // (pageable host memory: the copies have left the host arrays when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(QualityJob), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_specs, specs.data(), specs.size() * sizeof(WeightSpec), hipMemcpyHostToDevice, st));
+    if (x) NMRFIT_HIP(hipMemcpyAsync(d_x, x, (size_t)b->Dsum * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nr) {
+        NMRFIT_HIP(hipMemcpyAsync(d_rs, region_spec.data(), nr * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        NMRFIT_HIP(hipMemcpyAsync(d_edges, edges, 2 * nr * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    *n_rows = rows;
+    return launch_quality(st, d_jobs, K, quality_tiles(b->Nmax), b->Pmax, Rmax, d_specs, d_rs, (int64_t)nr, b->d_w_plain, d_edges, d_fl);
+}
+
 #pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
 extern "C" {
 
@@ -209,6 +292,40 @@ int nmrfit_batch_spectrum(nmrfit_batch *b, int32_t k, double *u_out, double *v_o
     if (k < 0 || k >= b->K) return refuse(NMRFIT_E_INVALID, "nmrfit_batch_spectrum: fit index out of range");
     const int q = part_of(b, k);
     return part_spectrum(b->parts[(size_t)q], k - b->first[(size_t)q], u_out, v_out);
+}
+
+int nmrfit_batch_quality_stats(nmrfit_batch *b, const double *x, const int32_t *R, const double *edges, double *out)
+{
+    const char *who = "nmrfit_batch_quality_stats";
+    int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    if (!out) return refuse(NMRFIT_E_INVALID, std::string(who) + ": null pointer");
+    std::vector<int64_t> N((size_t)b->K);
+    for (int32_t k = 0; k < b->K; ++k) N[(size_t)k] = b->noff[(size_t)k + 1] - b->noff[(size_t)k];
+    int64_t n_points = 0, n_regions = 0;
+    if ((rc = check_quality_args(who, b->K, N.data(), R, edges, &n_points, &n_regions)) != NMRFIT_OK) return rc;
+    if (!x && (rc = check_idle(b, who)) != NMRFIT_OK) return rc;
+    // every part enqueues its launches on its own stream; then the rows come back part after part and all streams are
+    // waited for.  A part's share of x, R, edges and out starts where the fits before it end.
+    std::vector<double *> d_rows(b->parts.size(), nullptr);
+    std::vector<int64_t> n_rows(b->parts.size(), 0);
+    int64_t r0 = 0;
+    for (size_t p = 0; p < b->parts.size() && rc == NMRFIT_OK; ++p) {
+        const int32_t f0 = b->first[p], f1 = b->first[p + 1];
+        rc = part_quality_enqueue(b->parts[p], x ? x + b->boff[(size_t)f0] : nullptr, R + f0, edges ? edges + 2 * r0 : nullptr, &d_rows[p],
+                                  &n_rows[p]);
+        for (int32_t k = f0; k < f1; ++k) r0 += R[k];
+    }
+    int64_t at = 0;
+    for (size_t p = 0; p < b->parts.size(); ++p) {
+        BatchPart *q = b->parts[p];
+        if (rc == NMRFIT_OK)
+            rc = staged_d2h(q->device, q->stream, out + at * kQualityRow, d_rows[p], (size_t)n_rows[p] * kQualityRow * sizeof(double));
+        at += n_rows[p];
+        const hipError_t e = hipStreamSynchronize(q->stream);
+        if (rc == NMRFIT_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(quality)", __FILE__, __LINE__);
+    }
+    return rc;
 }
 
 }  // extern "C"

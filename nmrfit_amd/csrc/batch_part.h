@@ -29,6 +29,7 @@ struct BatchPart {
     nmrfit::BatchFit *d_tables = nullptr;   // [9][K]: t = xp + 2 b + 4 pending (fused generations), 8 = plain evaluation
     double *d_summary = nullptr;         // [K][4]: generations, stop code, fg, best_f   (written by batch_tail_kernel)
     double *d_bestx = nullptr;           // [Dsum]: best_x rows, concatenated
+    const double *d_w_plain = nullptr;   // [sum of the fits' lengths]: the uploaded grids, plain order, NOT centred (the upload's landing buffer)
     std::vector<nmrfit::BatchFit> h_fits;   // host copy of table 0: every fit's array pointers and grid constants
     int64_t Psum = 0;
     // scratch of a reconstruction call in flight (nmrfit_batch_contributions): device block, and what goes where on the host
@@ -39,6 +40,9 @@ struct BatchPart {
         size_t bytes;
     };
     std::vector<ResultCopy> result_copies;
+    // the buffers of nmrfit_batch_quality_stats (job table, region tables, the tiles' sums, the rows): grown on demand
+    void *d_quality = nullptr;
+    size_t cap_quality = 0;
     // launch geometry: [0] workgroup = particle, [1] wave = particle
     nmrfit::BatchLaunch geom[2];
     bool geom_ok[2] = {false, false};

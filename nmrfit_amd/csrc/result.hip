@@ -8,30 +8,13 @@
 // (one fp64 division per peak and workgroup instead of per point).  The kernel is bound by what it writes -- (2 P + 6)
 // doubles per point -- and is launched once for a whole device batch (blockIdx.y = the fit): K x (2 P + 6) x N x 8 B,
 // 38 MB for 64 default-size fits, ~10 us of HBM time; the D2H copy that follows is what costs.
-#include "objective_math.h"
 #include "result_internal.h"
+#include "result_point.h"
 
 #include <algorithm>
 
 namespace nmrfit {
 namespace {
-
-// the per-peak constants the lines are evaluated from (the same as the objective kernels': nmrfit_internal.h, PeakLor)
-__device__ __forceinline__ PeakLor peak_record(const double *__restrict__ x, int k, double w0, double wspan)
-{
-    const double r = x[2];
-    const double width = x[4 + 3 * k], loc = x[5 + 3 * k], a = x[6 + 3 * k];
-    const double ihw = 2.0 / width;
-    const double locc = loc - w0;
-    const double lim = 1.0e18 / (wspan + fabs(locc));
-    PeakLor rec;   // (a width below the floor: the record of the floor width, as in objective_kernel.h)
-    rec.ihw = (fabs(ihw) > lim) ? copysign(lim, ihw) : ihw;
-    rec.c = -locc * rec.ihw;
-    const double ia = __builtin_isinf(ihw) ? ihw : rec.ihw;   // (width 0: non-finite, like the reference)
-    rec.al = a * r * ia * kInvPi;
-    rec.ag2 = 2.0 * a * (1.0 - r) * ia * kSqrtLn2OverPi;
-    return rec;
-}
 
 __device__ __forceinline__ void result_body(const ResultJob &job, PeakLor *__restrict__ recs)
 {
@@ -40,26 +23,14 @@ __device__ __forceinline__ void result_body(const ResultJob &job, PeakLor *__res
     const int64_t n_data = job.data ? job.N : 0;
     if (first >= job.Nout && first >= n_data) return;   // (a table's fits may differ in length: whole workgroups leave)
     const double *__restrict__ x = job.x;
-    for (int k = threadIdx.x; k < P; k += kResultThreads) recs[k] = peak_record(x, k, job.w0, job.wspan);
-    __syncthreads();
+    stage_peak_records<kResultThreads>(recs, x, P, job.w0, job.wspan);
     const int64_t j = first + threadIdx.x;
     const double p0 = x[0], p1 = x[1], yoff = x[3];
     if (j < job.Nout) {
         const int64_t Nout = job.Nout;
         const double wj = job.w_plain ? job.w_plain[j] - job.w0 : job.wc[grid_slot(j)];
-        // utils.py:262-277: real, imag per peak; V_fit = V_fit + real, I_fit = I_fit + imag, peak after peak from zero
-        double V = 0.0, I = 0.0;
-        for (int k = 0; k < P; ++k) {
-            const PeakLor rec = recs[k];
-            const double t = __builtin_fma(wj, rec.ihw, rec.c);
-            const double s = __builtin_fma(t, t, 1.0);
-            const double re = yoff + __builtin_fma(rec.al, rcp64(s), rec.ag2 * exp2_neg(-s));
-            const double im = dispersion(wj, rec);
-            if (job.real) job.real[(int64_t)k * Nout + j] = re;
-            if (job.imag) job.imag[(int64_t)k * Nout + j] = im;
-            V = V + re;
-            I = I + im;
-        }
+        double V, I;
+        point_lines<true>(recs, P, wj, yoff, job.real ? job.real + j : nullptr, job.imag ? job.imag + j : nullptr, Nout, &V, &I);
         if (job.fit) {
             // proc_autophase.ps2(V_fit, I_fit, inv=True, p0, p1) (proc_autophase.py:29-36): the ramp (p1 * j) / size over
             // the OUTPUT grid's index, rotation by 1 / exp(i phi)
@@ -73,15 +44,12 @@ __device__ __forceinline__ void result_body(const ResultJob &job, PeakLor *__res
         }
     }
     if (j < n_data) {
-        // ps2(u, v, p0, p1): V = cos phi u - sin phi v, I = sin phi u + cos phi v, phi_j = p0 + (p1 j) / N
         const int64_t N = job.N;
-        const double phi = p0 + (p1 * (double)j) / (double)N;
-        double sn, cs;
-        sincos_fast(phi, &sn, &cs);
         const int64_t slot = grid_slot(j);
-        const double uj = job.u[slot], vj = job.v[slot];
-        job.data[j] = cs * uj - sn * vj;
-        job.data[N + j] = sn * uj + cs * vj;
+        double dV, dI;
+        point_data(job.u[slot], job.v[slot], p0, p1, j, N, &dV, &dI);
+        job.data[j] = dV;
+        job.data[N + j] = dI;
     }
 }
 

@@ -156,15 +156,22 @@ void weights_layout(int32_t S, const int64_t *N, const int32_t *R, std::vector<W
     }
 }
 
+int launch_weights_nearest(hipStream_t st, const WeightSpec *specs, const int32_t *region_spec, int64_t n_regions,
+                           const double *w, const double *edges, int64_t *first_last)
+{
+    if (n_regions <= 0) return NMRFIT_OK;
+    hipLaunchKernelGGL(weights_nearest_kernel, dim3((unsigned)n_regions), dim3(kNearThreads), 0, st, specs, region_spec, w,
+                       edges, first_last);
+    NMRFIT_HIP(hipGetLastError());
+    return NMRFIT_OK;
+}
+
 int launch_weights(hipStream_t st, int32_t S, const WeightSpec *specs, const int32_t *region_spec, int64_t n_regions,
                    int64_t Nmax, const double *w, const double *edges, const double *level, int64_t *first_last,
                    double *out)
 {
-    if (n_regions > 0) {
-        hipLaunchKernelGGL(weights_nearest_kernel, dim3((unsigned)n_regions), dim3(kNearThreads), 0, st, specs, region_spec,
-                           w, edges, first_last);
-        NMRFIT_HIP(hipGetLastError());
-    }
+    const int rc = launch_weights_nearest(st, specs, region_spec, n_regions, w, edges, first_last);
+    if (rc != NMRFIT_OK) return rc;
     const dim3 grid((unsigned)((Nmax + kTile - 1) / kTile), (unsigned)S);
     hipLaunchKernelGGL(weights_fill_smooth_kernel, grid, dim3(kSmoothThreads), 0, st, specs, level, first_last, out);
     NMRFIT_HIP(hipGetLastError());

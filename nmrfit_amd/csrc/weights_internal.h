@@ -27,6 +27,11 @@ int check_weight_regions(const char *who, int32_t S, const int64_t *N, const int
 void weights_layout(int32_t S, const int64_t *N, const int32_t *R, std::vector<WeightSpec> *specs,
                     std::vector<int32_t> *region_spec);
 
+// The first of the two launches below on its own (quality.hip takes its region edges from it: the rule is written once):
+// the nearest grid point to both edges of every region into first_last (2 int64 per region, sorted).  No region: nothing.
+int launch_weights_nearest(hipStream_t st, const WeightSpec *specs, const int32_t *region_spec, int64_t n_regions,
+                           const double *w, const double *edges, int64_t *first_last);
+
 // The two launches on `st` (device pointers): the nearest grid point to both edges of every region into first_last
 // (2 int64 per region, sorted), then fill + ten smoothing sweeps of every spectrum into out (sum N doubles, laid out
 // like w).  n_regions = sum R (0: one launch), Nmax = the longest spectrum.

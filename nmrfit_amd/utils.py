@@ -458,6 +458,20 @@ class FitUtility:
         self.real_contribs = [real[k] for k in range(real.shape[0])]
         self.imag_contribs = [imag[k] for k in range(imag.shape[0])]
 
+    def residual_stats(self, regions=None):
+        """The ``quality.FitQuality`` of this finished fit: the residual V_fit - V_data at ``params`` reduced on the
+        device (nmrfit_quality_stats, csrc/quality.hip; what plot.residual draws, as numbers) per region, over the whole
+        grid and over what no region holds.  ``regions``: a list of ``(lo, hi)`` in units of w; default: the peaks'
+        bounds.  Kept as ``self.quality``."""
+        from . import quality
+        if 'params' not in self.__dict__:      # (not hasattr: __getattr__ answers for missing names)
+            raise AttributeError("residual_stats: this fit has no params yet (call fit() first)")
+        if regions is None:
+            regions = [tuple(p.bounds) for p in self.data.peaks]
+        self.quality = quality.residual_stats(self.data.w, self.data.u, self.data.v, self.params, regions,
+                                              device=self._device())
+        return self.quality
+
     def get_areas(self):
         """utils.py:312-322."""
         return np.array([self.params[i] for i in range(6, len(self.params), 3)])
