@@ -211,7 +211,9 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     int wpb = kWavesPerBlock, slices = 0, rows = 0;
     copies(wpb, &slices, &rows);
     size_t lds = objective_lds(ctx->variant, P, dR != nullptr, fit_im, &variant, &aux_off, wpb, slices, rows);
-    if (rows_im && variant != NMRFIT_VARIANT_DEFAULT) {
+    // (the context's own variant too: STAGED runs the DEFAULT kernel wherever the imaginary channel is on, and would
+    // answer here with DEFAULT's rows where include/nmrfit_amd_lsq_im.h promises a refusal)
+    if (rows_im && (variant != NMRFIT_VARIANT_DEFAULT || ctx->variant != NMRFIT_VARIANT_DEFAULT)) {
         set_error("residual rows with the imaginary channel exist for the DEFAULT kernel variant only (and while its LDS records fit)");
         return NMRFIT_E_UNSUPPORTED;
     }

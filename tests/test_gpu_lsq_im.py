@@ -12,6 +12,13 @@ fit_many(batch_polish="both"); the refusals.
 Shapes, the smallest that cross each boundary: N = 1, 63, 64, 65 (the LSQ tile of 64, full and ragged), 511, 512, 513 (the
 512-point chunk), 1537 (four chunks = four blocks: the workgroup holds the particle), N_MULTI (blocks of two chunks,
 hp_truth.block_len); P = 1, 2, 3 everywhere, P = 24 (D = 76, the reduction kernel's largest) and P = 25 (beyond it) once.
+
+What this file covers of the rows, and what it does not: synth spectra at three parameter rows (inside the box, one needle,
+one centred peak) with at most three peaks -- never a second group of eight, the Gaussian window's edge from outside the
+chunk, the Dawson table's boundaries, a width below the floor, a negative width or r outside [0, 1].  Those, P up to 130,
+the five classes of the kernel's form switches, weights with zeros and a negative value, and the real rows against the same
+truth (here they are tied to nmrfit_residual_batch bit for bit, no more) are in tests/test_gpu_rows_pointwise.py; so is
+the batch at such points.
 """
 import math
 

@@ -16,7 +16,10 @@ launch that leaves per-block sums to finalize_kernel).  The features above inclu
 amplitudes, which put every particle with 32 peaks or more, and most smaller ones, on the kernel's GENERAL forms: the
 Lorentzian group form and the point-by-point Gaussian.  The two-operation pair form and the Gaussian recurrence
 (objective_kernel.h fast_all / rec_all), rows 2 to 6, peak counts 0, 2 to 7 and 10 to 15, the other launch forms and
-the swarm / batch boxes that reach the recurrence are held to truth in tests/test_gpu_pointwise_forms.py.
+the swarm / batch boxes that reach the recurrence are held to truth in tests/test_gpu_pointwise_forms.py.  One-hot weights
+reach the objective launches alone: the residual ROWS (nmrfit_residual_batch, the rows of both channels, the batch's
+normal equations) are written by instantiations of their own -- a row store, no Gaussian recurrence -- and are held to
+truth, at the particles built here and under weights that are not ones, in tests/test_gpu_rows_pointwise.py.
 
 Each test prints its worst err/tol ratio.
 """

@@ -441,3 +441,140 @@ def test_kernel_forms_recurrence_clauses():
     assert narrow > 64 * h                                                           # (|d| <= 2 holds for both)
     assert hp.kernel_forms(_particle(0.5, [[wide, 3.5, 1.0]]), bent)["rec"]
     assert not hp.kernel_forms(_particle(0.5, [[narrow, 3.5, 1.0]]), bent)["rec"]
+
+
+# ---- residual rows: the float64 references inside the plain bound, planted errors outside ---------------------------------
+
+def _reference_rows(X, w, u, v, wt):
+    """{channel: rows} of the float64 references: the C oracle (real) and tests/lsq_im_support.py (imaginary, both modes)."""
+    from oracle import c_oracle
+    from tests import lsq_im_support as M
+    return {"re": c_oracle.residual_batch(X, w, u, v, wt)[0], "im1": M.residual_rows(X, w, u, v, wt, 1)[1],
+            "im2": M.residual_rows(X, w, u, v, wt, 2)[1]}
+
+
+def _check_reference(worst, key, X, w, u, v, wt, j):
+    from tests import rows_support as RS
+    rows = _reference_rows(X, w, u, v, wt)
+    for s, x in enumerate(X):
+        t = RS.truth(key + (j, X.shape[1], s), x, w, u, v, j)
+        for ch, R in rows.items():
+            RS.check_point(worst[ch], R[s, j], t, ch, wt[j], (j, (X.shape[1] - 4) // 3, s))
+
+
+def _report(worst):
+    fails = []
+    for wo in worst.values():
+        fails += wo.report()
+    return fails
+
+
+@pytest.mark.parametrize("kind", ["uniform", "descending", "nonuniform", "unsorted"])
+def test_float64_references_of_the_rows_at_the_switches_stay_inside_the_plain_bound(kind):
+    """The cases of tests/test_gpu_rows_pointwise.py test_rows_at_the_switches, at the probes 0, 64, 511, 512 and N - 1,
+    every peak count (65 and 130 at two of the probes), the P = 0 row, the same weights: what the bound asks of the
+    device it grants a plain float64 evaluation with room to spare.  Worst err/tol measured over the four grids: real rows
+    (C oracle) 0.0614 (nonuniform, point 64, P = 9, row 0; 0.037 on the other grids), imaginary rows (numpy, scipy's
+    dawsn) 0.0102 in either mode (unsorted, point 0, the P = 0 row)."""
+    from tests import rows_support as RS
+    w, u, v = RS.make_grid(kind)
+    N = w.size
+    js = RS.switch_probes(N)
+    wt, _ = RS.hostile_weights(N, js, seed=5)
+    worst = {ch: hp.Worst("reference rows/%s/%s" % (kind, ch)) for ch in RS.CHANNELS}
+    for n, j in enumerate(js):
+        if j not in (0, 64, 511, 512, N - 1):
+            continue
+        for P, X in RS.switch_stacks(w, n, j).items():
+            _check_reference(worst, (kind, N), X, w, u, v, wt, j)
+        _check_reference(worst, (kind, N), RS.X_NO_PEAK, w, u, v, wt, j)
+    fails = _report(worst)
+    assert not fails, fails[:5]
+
+
+@pytest.mark.parametrize("cls", ["pair_rec", "pair", "general_rec", "general", "budget_rec"])
+def test_float64_references_of_class_rows_stay_inside_the_plain_bound(cls):
+    """Every form class of tests/test_gpu_pointwise_forms.py on uniform1101: one probe in the full chunk, one in the
+    ragged tail (the grid's last point), every peak count.  The *_rec classes included: a plain evaluation has no
+    recurrence, and neither have the row kernels.  Worst err/tol measured over the five classes: real rows 0.0119,
+    imaginary rows 0.0119 (both general_rec, point 512)."""
+    from tests import rows_support as RS
+    grid = "uniform1101"
+    w, u, v = RS.class_grid(grid)
+    N = w.size
+    frame = hp.grid_analysis(w)
+    chunks, large = RS.class_probes(N, cls)
+    probes = [j for _, _, p in chunks for _, j in p]
+    wt, _ = RS.hostile_weights(N, probes, seed=9)
+    worst = {ch: hp.Worst("reference rows/%s/%s/%s" % (grid, cls, ch)) for ch in RS.CHANNELS}
+    for kind, c, p in chunks:
+        stacks = RS.class_stacks(w, c, cls, frame)
+        j = [j for _, j in p if j in large][0]
+        for P, X in stacks.items():
+            _check_reference(worst, (grid, kind, cls), X, w, u, v, wt, j)
+    fails = _report(worst)
+    assert not fails, fails[:5]
+
+
+def _ratio(got, t, ch, wj):
+    from tests import rows_support as RS
+    val, tol = RS.CHANNELS[ch]
+    return abs(got - wj * t[val]) / (abs(wj) * t[tol])
+
+
+def test_planted_errors_in_a_row_leave_the_bound():
+    """The GPU test's comparison discriminates: a float64 row passes, the same row with one planted error does not.
+        (a) one peak's Lorentzian amplitude off by a relative 1e-12, read at the peak's centre;
+        (b) the Gaussian of a general-form particle (r = 0) dropped at a point just inside its window's edge
+            (1 - 1e-6 of 3.97 widths), on data that is zero there -- with data of order one the value at the edge, 2^-63 of
+            the amplitude, lies below the bound by design of the window; dropped at three widths it is flagged in noise;
+        (c) the row shifted by one grid point (a store index off by one);
+        (d) the weight's sign lost, read at the point whose weight is negative."""
+    from tests import rows_support as RS
+    from tests.test_gpu_pointwise import features
+    w, u, v = RS.make_grid("uniform")
+    N = w.size
+    js = RS.switch_probes(N)
+    wt, _ = RS.hostile_weights(N, js, seed=5)
+    j = 64
+    # (a) the t = 0 feature alone, with a Lorentzian part (the builder's row has r = 0)
+    x = RS.particles(w, j)[1][0].copy()
+    x[2] = 0.37
+    assert x[5] == w[j]
+    t = hp.point(x, w, u, v, j)
+    row = _reference_rows(x[None, :], w, u, v, wt)["re"][0]
+    AL = x[6] * x[2] * 2.0 / (math.pi * x[4])
+    assert _ratio(row[j], t, "re", wt[j]) < 1.0
+    assert _ratio(row[j] - wt[j] * AL * 1e-12, t, "re", wt[j]) > 1.0
+    # (b) features 2 (the window's edge, inside by 1e-6) and 8 (three widths)
+    feats = features(w, j)
+    z = np.zeros(N)
+    for k, uu, vv in ((2, z, z), (8, u, v)):
+        width, loc, a, kind = feats[k]
+        assert kind == "gauss"
+        assert abs(abs(w[j] - loc) / width - ((1 - 1e-6) * 3.9686269665968861 if k == 2 else 3.0)) < 1e-9
+        x = np.array([0.0, 0.0, 0.0, 0.0, width, loc, a])
+        assert not hp.kernel_forms(x, w)["fast"]                        # r = 0: the general form
+        t = hp.point(x, w, uu, vv, j)
+        row = _reference_rows(x[None, :], w, uu, vv, wt)["re"][0]
+        G = row[j] - wt[j] * t["V"]                                      # the model's part of the row: -weights G
+        assert G != 0.0
+        assert _ratio(row[j], t, "re", wt[j]) < 1.0
+        assert _ratio(row[j] - G, t, "re", wt[j]) > 1.0, k
+    # (c), (d) a stack of the sweep, all three channels
+    X = RS.particles(w, j)[9]
+    rows = _reference_rows(X, w, u, v, wt)
+    neg = [q for q in js if wt[q] < 0]
+    assert len(neg) == 1
+    Xn = RS.particles(w, neg[0])[9]
+    rows_n = _reference_rows(Xn, w, u, v, wt)
+    for ch in RS.CHANNELS:
+        for s, x in enumerate(X):
+            t = RS.truth(("uniform", N, j, X.shape[1], s), x, w, u, v, j)
+            assert _ratio(rows[ch][s, j], t, ch, wt[j]) < 1.0
+            for shift in (1, -1):
+                assert _ratio(np.roll(rows[ch][s], shift)[j], t, ch, wt[j]) > 1.0, (ch, s, shift)
+        for s, x in enumerate(Xn):
+            t = hp.point(x, w, u, v, neg[0])
+            assert _ratio(rows_n[ch][s, neg[0]], t, ch, wt[neg[0]]) < 1.0
+            assert _ratio(-rows_n[ch][s, neg[0]], t, ch, wt[neg[0]]) > 1.0, (ch, s)
