@@ -46,18 +46,16 @@ enum {
 };
 
 /* Kernel variants (numerics identical to <= 1e-12 relative).  DEFAULT, FARFIELD and NOREC are in every build of the
- * library; BASELINE, NOSKIP, SINGLE, QUAD and STAGED are A/B forms the tuned kernels are measured and checked
+ * library; BASELINE and NOSKIP are A/B forms the tuned kernels are measured and checked
  * against: they exist in libnmrfit_amd_ab.so only (nmrfit_amd/csrc/build.sh --ab), and nmrfit_ctx_set_variant
- * answers NMRFIT_E_UNSUPPORTED for them in the product library. */
+ * answers NMRFIT_E_UNSUPPORTED for them in the product library.  The numbers 3, 4 and 5 belonged to A/B forms since
+ * retired and stay unused: NMRFIT_E_INVALID in every build. */
 enum {
     NMRFIT_VARIANT_DEFAULT = 0,   /* tuned fp64: 8 Lorentzians x 4 points per reciprocal (scaled pair form
                                      for positive amplitudes) + Gaussian window skip (+ Gaussian
                                      recurrence on uniform grids, see NOREC)                          */
     NMRFIT_VARIANT_BASELINE = 1,  /* plain fp64: IEEE divide + libdevice exp2 per unit, no skipping  */
     NMRFIT_VARIANT_NOSKIP = 2,    /* tuned arithmetic, Gaussian evaluated everywhere                 */
-    NMRFIT_VARIANT_SINGLE = 3,    /* one reciprocal per unit + Gaussian window skip                  */
-    NMRFIT_VARIANT_QUAD = 4,      /* 4 Lorentzians per reciprocal + Gaussian window skip             */
-    NMRFIT_VARIANT_STAGED = 5,    /* DEFAULT + LDS-DMA staging of u/v/weights (pays only for P <= 2)  */
     NMRFIT_VARIANT_FARFIELD = 6,  /* opt-in: Lorentzian tails of distant peaks through one shared
                                      Taylor expansion per 512-point chunk (truncation <= 1e-16 of each
                                      term); not the default because it changes the per-unit work      */

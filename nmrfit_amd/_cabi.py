@@ -11,7 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libnmrfit_amd.so")
-# the A/B library: the product + the A/B kernel variants (BASELINE, NOSKIP, SINGLE, QUAD, STAGED); what the reference
+# the A/B library: the product + the A/B kernel variants (BASELINE, NOSKIP); what the reference
 # kernels of the parity tests, tools/ab.py and bench.py's `variants` entry load.  NMRFIT_LIB=<path> makes it (or any
 # other build) the library of this process.
 AB_LIB_PATH = os.path.join(_HERE, "lib", "libnmrfit_amd_ab.so")
@@ -21,15 +21,14 @@ OK = 0
 E_INVALID, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_STATE, E_COMM = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
 FIT_IM_OFF, FIT_IM_REFERENCE, FIT_IM_SUM = 0, 1, 2
-VARIANT_DEFAULT, VARIANT_BASELINE, VARIANT_NOSKIP, VARIANT_SINGLE, VARIANT_QUAD, VARIANT_STAGED, VARIANT_FARFIELD = 0, 1, 2, 3, 4, 5, 6
+VARIANT_DEFAULT, VARIANT_BASELINE, VARIANT_NOSKIP, VARIANT_FARFIELD = 0, 1, 2, 6     # (3, 4, 5: retired A/B forms, unused)
 VARIANT_NOREC = 7
 VARIANT_FARFIELD32 = 8     # opt-in mixed precision: the far-field kernel's shared polynomial in packed fp32
 HANDOVER_FAST, HANDOVER_FENCED, HANDOVER_TWO_LAUNCH = 0, 1, 2
 ABI_VERSION = 6
 PHASE_ACME, PHASE_PEAK_MINIMA, PHASE_BRUTE_LEVEL = 0, 1, 2
 _MAX_SPECTRA_PER_CALL = 65535     # the library's limit per call (a launch's grid.y / grid.x): larger lists are cut
-_VARIANT_NAMES = {"default": 0, "baseline": 1, "noskip": 2, "single": 3, "quad": 4, "staged": 5, "farfield": 6,
-                  "norec": 7, "farfield32": 8}
+_VARIANT_NAMES = {"default": 0, "baseline": 1, "noskip": 2, "farfield": 6, "norec": 7, "farfield32": 8}
 
 
 def variant_id(v):
@@ -257,7 +256,7 @@ def lib_path():
 
 
 def has_ab_variants():
-    """True when the loaded library is an A/B build (the BASELINE / NOSKIP / SINGLE / QUAD / STAGED kernels exist)."""
+    """True when the loaded library is an A/B build (the BASELINE / NOSKIP kernels exist)."""
     return bool(lib().nmrfit_diag_ab_build())
 
 
@@ -267,8 +266,7 @@ PRODUCT_VARIANTS = (VARIANT_DEFAULT, VARIANT_FARFIELD, VARIANT_NOREC, VARIANT_FA
 def available_variants():
     """Kernel variants of the loaded library: the three product kernels, plus the A/B forms in an A/B build."""
     if has_ab_variants():
-        return [VARIANT_DEFAULT, VARIANT_BASELINE, VARIANT_NOSKIP, VARIANT_SINGLE, VARIANT_QUAD, VARIANT_STAGED,
-                VARIANT_FARFIELD, VARIANT_NOREC, VARIANT_FARFIELD32]
+        return [VARIANT_DEFAULT, VARIANT_BASELINE, VARIANT_NOSKIP, VARIANT_FARFIELD, VARIANT_NOREC, VARIANT_FARFIELD32]
     return list(PRODUCT_VARIANTS)
 
 

@@ -3,7 +3,7 @@
 # (the objective kernel's instantiations are one unit per selectable variant) and are then linked.
 # Usage: nmrfit_amd/csrc/build.sh [extra hipcc flags]
 #        nmrfit_amd/csrc/build.sh --ab      the A/B library libnmrfit_amd_ab.so: the product + the A/B kernel variants
-#                                           (BASELINE, NOSKIP, SINGLE, QUAD, STAGED) and the diagnostic entry points of
+#                                           (BASELINE, NOSKIP) and the diagnostic entry points of
 #                                           include/nmrfit_amd_diag.h -- what tools/ab.py, bench.py's `variants` entry
 #                                           and the parity tests' reference kernels use
 #        NMRFIT_LIBNAME=libab_x.so nmrfit_amd/csrc/build.sh -DSOMETHING=2   (one-off A/B builds for tools/ab.py)

@@ -49,10 +49,16 @@ void analyse_grid(const double *w, int64_t N, double *w0_out, double *wspan_out,
 }
 
 // the kernel variants this library holds: every one in the A/B build, the selectable four in the product
+// (3, 4 and 5 were A/B forms since retired: the numbers stay unused)
+static bool variant_known(int variant)
+{
+    return variant == NMRFIT_VARIANT_DEFAULT || variant == NMRFIT_VARIANT_BASELINE || variant == NMRFIT_VARIANT_NOSKIP ||
+           variant == NMRFIT_VARIANT_FARFIELD || variant == NMRFIT_VARIANT_NOREC || variant == NMRFIT_VARIANT_FARFIELD32;
+}
 static bool variant_built(int variant)
 {
 #ifdef NMRFIT_AB_BUILD
-    return variant >= 0 && variant <= NMRFIT_VARIANT_FARFIELD32;
+    return variant_known(variant);
 #else
     return variant == NMRFIT_VARIANT_DEFAULT || variant == NMRFIT_VARIANT_FARFIELD || variant == NMRFIT_VARIANT_NOREC ||
            variant == NMRFIT_VARIANT_FARFIELD32;
@@ -191,7 +197,7 @@ int nmrfit_ctx_set_stream(nmrfit_ctx *ctx, void *hip_stream)
 
 int nmrfit_ctx_set_variant(nmrfit_ctx *ctx, int variant)
 {
-    if (!ctx || variant < 0 || variant > NMRFIT_VARIANT_FARFIELD32) {
+    if (!ctx || !variant_known(variant)) {
         set_error("bad context or variant");
         return NMRFIT_E_INVALID;
     }

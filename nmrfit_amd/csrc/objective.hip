@@ -3,6 +3,7 @@
 // (block-sum finalisation, grid preparation; the post-fit reconstruction is result.hip).  The objective kernel is
 // objective_kernel.h; its instantiations live in objective_{default,farfield,norec}.hip.
 #include "objective_launch.h"
+#include "objective_lds.h"
 #include "objective_math.h"
 
 #include <algorithm>
@@ -88,55 +89,92 @@ int scatter_grid(nmrfit_ctx *ctx, const double *d_src, double *d_dst)
 // implement the imaginary part) and the dynamic LDS its per-wave records need.
 constexpr size_t kStaticLds = kObjectiveStaticLds;   // objective_kernel's own __shared__ (wsums) + alignment slack
 static_assert(kObjectiveStaticLds == (size_t)kWsumsCount * sizeof(double) + 64, "objective_launch.h and objective_math.h disagree");
-// `slices`: copies of the per-peak records in a workgroup (1 when its waves are segments of one particle, else wpb);
-// `rows`: copies of the updated row kept for a fused swarm generation (0: none)
-size_t objective_lds(int variant, int32_t P, bool residual, int fit_im, int *variant_out, unsigned *aux_off, int wpb,
-                     int slices, int rows)
+namespace {
+struct ResolvedLds {
+    int variant;
+    size_t lds;
+    unsigned aux_off;
+};
+// Every size is the `end` of the kernel's own layout (objective_lds.h); here is only the fallback rule.
+constexpr ResolvedLds resolve_lds(int variant, int32_t P, bool residual, int fit_im, int wpb, int slices, int rows)
 {
     // the mixed-precision far-field kernel exists for objective launches without the imaginary channel; everything else
     // of a context set to it runs the fp64 far-field kernel (same records, same LDS)
     const bool want32 = variant == NMRFIT_VARIANT_FARFIELD32;
     if (want32) variant = NMRFIT_VARIANT_FARFIELD;
-    const size_t np = (size_t)std::max(P, 1);
+    const int np = P > 1 ? P : 1;
     // what a workgroup may take of a CU's 160 KiB for the records sized here: everything but the kernel's static
     // LDS and (swarm generations) the per-wave copies of the updated rows that launch_objective appends
     const size_t room = 160 * 1024 - kStaticLds -
                         (rows ? (size_t)rows * (size_t)(4 + 3 * (int64_t)P) * sizeof(double) + 16 : 0);
-    const size_t lds_recs = (((size_t)slices * np * (sizeof(PeakLor) + sizeof(PeakWin)) + 15) & ~(size_t)15) +
-                            (size_t)wpb * kMaxBlocks * sizeof(double2) + kSharedPrologueBytes +
-                            (slices == 1 ? 0 : (size_t)wpb * 2 * kWave * sizeof(double));   // per-wave lane phase seeds
-    const size_t lds_stage = (size_t)wpb * 3 * kChunk * sizeof(double);
-    const size_t lds_far = (size_t)wpb * far_stride(fit_im) * sizeof(double);
-    // Gaussian recurrence constants (d, C) per peak: objective launches of DEFAULT / FARFIELD
-    const size_t lds_rec = residual ? 0 : (size_t)slices * np * sizeof(double2);
-    const size_t lds_fast = (size_t)slices * np * sizeof(PeakFast);   // scaled records of the two-operation pair form (DEFAULT)
-    // the all-peak imaginary model sums far peaks through the far-field scratch and evaluates Dawson's
-    // integral from a table in LDS
-    const size_t lds_im = (fit_im == 2) ? lds_far : 0;
-    // (fit_im == 1 reads the same table: gathered intervals near the last peak, the asymptotic series elsewhere)
-    const size_t lds_tab = (fit_im != 0) ? (size_t)kDawTabCount * sizeof(double) + 16 : 0;
-    // the imaginary channel exists in DEFAULT, NOREC and FARFIELD; the A/B variants fail in launch_variant
-    if (variant == NMRFIT_VARIANT_STAGED && fit_im != 0) variant = NMRFIT_VARIANT_DEFAULT;
-    // STAGED needs three workgroups to still fit in a CU's 160 KiB (P <= 27); beyond that it
-    // runs the unstaged kernel.
-    if (variant == NMRFIT_VARIANT_STAGED && 3 * (lds_recs + lds_stage + kStaticLds) > 160 * 1024) variant = NMRFIT_VARIANT_DEFAULT;
-    if (variant == NMRFIT_VARIANT_FARFIELD && lds_recs + lds_far + lds_rec + lds_tab + 16 > room)
+    // (the imaginary channel exists in DEFAULT, NOREC and FARFIELD; the A/B variants fail in launch_variant)
+    if (variant == NMRFIT_VARIANT_FARFIELD && objective_lds_layout(variant, residual, fit_im, np, wpb, slices).end + 16 > room)
         variant = NMRFIT_VARIANT_DEFAULT;   // P > ~600
-    if (variant == NMRFIT_VARIANT_DEFAULT && lds_recs + lds_im + lds_rec + lds_fast + lds_tab + 16 > room)
+    if (variant == NMRFIT_VARIANT_DEFAULT && objective_lds_layout(variant, residual, fit_im, np, wpb, slices).end + 16 > room)
         variant = NMRFIT_VARIANT_NOREC;     // P > ~450: no room for the recurrence / scaled records
-    size_t lds = lds_recs + (variant == NMRFIT_VARIANT_STAGED ? lds_stage : 0) +
-                 (variant == NMRFIT_VARIANT_FARFIELD ? lds_far : lds_im) +
-                 ((variant == NMRFIT_VARIANT_FARFIELD || variant == NMRFIT_VARIANT_DEFAULT) ? lds_rec : 0) +
-                 (variant == NMRFIT_VARIANT_DEFAULT ? lds_fast : 0);
-    *aux_off = 0;
-    if (lds_tab) {
-        lds = (lds + 15) & ~(size_t)15;
-        *aux_off = (unsigned)lds;
-        lds += lds_tab;
-    }
+    const ObjectiveLds at = objective_lds_layout(variant, residual, fit_im, np, wpb, slices);
     if (want32 && variant == NMRFIT_VARIANT_FARFIELD && !residual && fit_im == 0) variant = NMRFIT_VARIANT_FARFIELD32;
-    *variant_out = variant;
-    return lds;
+    return ResolvedLds{variant, at.end, fit_im != 0 ? (unsigned)at.tab : 0u};
+}
+// The totals of the hand-added formula this function replaced, on both sides of every switch: a change of the layout
+// that moves the host's answer by a byte does not compile.  Columns: objective / residual launch x fit_im 0, 1, 2 x
+// (4 waves: one copy of the records, four; 8 waves: one copy, eight), no fused rows.
+struct LdsPin {
+    int variant, P;
+    size_t lds[24];
+};
+constexpr LdsPin kLdsPins[] = {
+    {NMRFIT_VARIANT_DEFAULT, 1, {2224, 6576, 3248, 12048, 7968, 12320, 8992, 17792, 43808, 48160, 80672, 89472, 2208, 6512, 3232, 11920, 7952, 12256, 8976, 17664, 43792, 48096, 80656, 89344}},
+    {NMRFIT_VARIANT_DEFAULT, 6, {2656, 8336, 3680, 15568, 8400, 14080, 9424, 21312, 44240, 49920, 81104, 92992, 2560, 7952, 3584, 14800, 8304, 13696, 9328, 20544, 44144, 49536, 81008, 92224}},
+    {NMRFIT_VARIANT_DEFAULT, 32, {4944, 17488, 5968, 33872, 10688, 23232, 11712, 39616, 46528, 59072, 83392, 111296, 4432, 15440, 5456, 29776, 10176, 21184, 11200, 35520, 46016, 57024, 82880, 107200}},
+    {NMRFIT_VARIANT_DEFAULT, 33, {5040, 17840, 6064, 34576, 10784, 23584, 11808, 40320, 46624, 59424, 83488, 112000, 4512, 15728, 5536, 30352, 10256, 21472, 11280, 36096, 46096, 57312, 82960, 107776}},
+    {NMRFIT_VARIANT_DEFAULT, 132, {13744, 52688, 14768, 104272, 19488, 58432, 20512, 110016, 55328, 94272, 92192, 131008, 11632, 44240, 12656, 87376, 17376, 49984, 18400, 93120, 53216, 85824, 90080, 131008}},
+    {NMRFIT_VARIANT_DEFAULT, 133, {13840, 53040, 14864, 104976, 19584, 58784, 20608, 110720, 55424, 94624, 92288, 131328, 11712, 44528, 12736, 87952, 17456, 50272, 18480, 93696, 53296, 86112, 90160, 131328}},
+    {NMRFIT_VARIANT_DEFAULT, 452, {41904, 78544, 42928, 155984, 47648, 84288, 48672, 161728, 83488, 120128, 120352, 233408, 34672, 136400, 35696, 155984, 40416, 142144, 41440, 161728, 76256, 120128, 113120, 233408}},
+    {NMRFIT_VARIANT_DEFAULT, 606, {55456, 103184, 56480, 205264, 61200, 108928, 62224, 211008, 97040, 144768, 133904, 282688, 45760, 103184, 46784, 205264, 51504, 108928, 52528, 211008, 87344, 144768, 124208, 282688}},
+    {NMRFIT_VARIANT_DEFAULT, 960, {86608, 159824, 87632, 318544, 92352, 165568, 93376, 324288, 128192, 201408, 118976, 395968, 71248, 159824, 72272, 318544, 76992, 165568, 78016, 324288, 112832, 201408, 149696, 395968}},
+    {NMRFIT_VARIANT_FARFIELD, 1, {37008, 41264, 72848, 81424, 42752, 47008, 78592, 87168, 43776, 48032, 80640, 89216, 36992, 41200, 72832, 81296, 42736, 46944, 78576, 87040, 43760, 47968, 80624, 89088}},
+    {NMRFIT_VARIANT_FARFIELD, 6, {37280, 42384, 73120, 83664, 43024, 48128, 78864, 89408, 44048, 49152, 80912, 91456, 37184, 42000, 73024, 82896, 42928, 47744, 78768, 88640, 43952, 48768, 80816, 90688}},
+    {NMRFIT_VARIANT_FARFIELD, 32, {38736, 48208, 74576, 95312, 44480, 53952, 80320, 101056, 45504, 54976, 82368, 103104, 38224, 46160, 74064, 91216, 43968, 51904, 79808, 96960, 44992, 52928, 81856, 99008}},
+    {NMRFIT_VARIANT_FARFIELD, 33, {38800, 48432, 74640, 95760, 44544, 54176, 80384, 101504, 45568, 55200, 82432, 103552, 38272, 46320, 74112, 91536, 44016, 52064, 79856, 97280, 45040, 53088, 81904, 99328}},
+    {NMRFIT_VARIANT_FARFIELD, 132, {44336, 70608, 80176, 140112, 50080, 76352, 85920, 145856, 51104, 77376, 87968, 147904, 42224, 62160, 78064, 123216, 47968, 67904, 83808, 128960, 48992, 68928, 85856, 131008}},
+    {NMRFIT_VARIANT_FARFIELD, 133, {44400, 70832, 80240, 140560, 50144, 76576, 85984, 146304, 51168, 77600, 88032, 148352, 42272, 62320, 78112, 123536, 48016, 68064, 83856, 129280, 49040, 69088, 85904, 131328}},
+    {NMRFIT_VARIANT_FARFIELD, 452, {62256, 142288, 98096, 155984, 68000, 148032, 103840, 161728, 69024, 149056, 105888, 233408, 55024, 113360, 90864, 155984, 60768, 119104, 96608, 161728, 61792, 120128, 98656, 233408}},
+    {NMRFIT_VARIANT_FARFIELD, 606, {70880, 103184, 106720, 205264, 76624, 108928, 112464, 211008, 77648, 144768, 114512, 282688, 61184, 138000, 97024, 205264, 66928, 143744, 102768, 211008, 67952, 144768, 104816, 282688}},
+    {NMRFIT_VARIANT_FARFIELD, 960, {90704, 159824, 126544, 318544, 96448, 165568, 132288, 324288, 97472, 201408, 134336, 395968, 75344, 159824, 111184, 318544, 81088, 165568, 116928, 324288, 82112, 201408, 118976, 395968}},
+    {NMRFIT_VARIANT_NOREC, 1, {2176, 6384, 3200, 11664, 7920, 12128, 8944, 17408, 43760, 47968, 80624, 89088, 2176, 6384, 3200, 11664, 7920, 12128, 8944, 17408, 43760, 47968, 80624, 89088}},
+    {NMRFIT_VARIANT_NOREC, 6, {2368, 7184, 3392, 13264, 8112, 12928, 9136, 19008, 43952, 48768, 80816, 90688, 2368, 7184, 3392, 13264, 8112, 12928, 9136, 19008, 43952, 48768, 80816, 90688}},
+    {NMRFIT_VARIANT_NOREC, 32, {3408, 11344, 4432, 21584, 9152, 17088, 10176, 27328, 44992, 52928, 81856, 99008, 3408, 11344, 4432, 21584, 9152, 17088, 10176, 27328, 44992, 52928, 81856, 99008}},
+    {NMRFIT_VARIANT_NOREC, 33, {3456, 11504, 4480, 21904, 9200, 17248, 10224, 27648, 45040, 53088, 81904, 99328, 3456, 11504, 4480, 21904, 9200, 17248, 10224, 27648, 45040, 53088, 81904, 99328}},
+    {NMRFIT_VARIANT_NOREC, 132, {7408, 27344, 8432, 53584, 13152, 33088, 14176, 59328, 48992, 68928, 85856, 131008, 7408, 27344, 8432, 53584, 13152, 33088, 14176, 59328, 48992, 68928, 85856, 131008}},
+    {NMRFIT_VARIANT_NOREC, 133, {7456, 27504, 8480, 53904, 13200, 33248, 14224, 59648, 49040, 69088, 85904, 131328, 7456, 27504, 8480, 53904, 13200, 33248, 14224, 59648, 49040, 69088, 85904, 131328}},
+    {NMRFIT_VARIANT_NOREC, 452, {20208, 78544, 21232, 155984, 25952, 84288, 26976, 161728, 61792, 120128, 98656, 233408, 20208, 78544, 21232, 155984, 25952, 84288, 26976, 161728, 61792, 120128, 98656, 233408}},
+    {NMRFIT_VARIANT_NOREC, 606, {26368, 103184, 27392, 205264, 32112, 108928, 33136, 211008, 67952, 144768, 104816, 282688, 26368, 103184, 27392, 205264, 32112, 108928, 33136, 211008, 67952, 144768, 104816, 282688}},
+    {NMRFIT_VARIANT_NOREC, 960, {40528, 159824, 41552, 318544, 46272, 165568, 47296, 324288, 82112, 201408, 118976, 395968, 40528, 159824, 41552, 318544, 46272, 165568, 47296, 324288, 82112, 201408, 118976, 395968}},
+};
+constexpr bool lds_pins_hold()
+{
+    for (const LdsPin &p : kLdsPins) {
+        int c = 0;
+        for (int residual = 0; residual < 2; ++residual)
+            for (int fit_im = 0; fit_im < 3; ++fit_im)
+                for (int wpb = kWavesPerBlock; wpb <= kWideWaves; wpb += kWavesPerBlock)
+                    for (int slices = 1; slices <= wpb; slices += wpb - 1)
+                        if (resolve_lds(p.variant, p.P, residual != 0, fit_im, wpb, slices, 0).lds != p.lds[c++]) return false;
+    }
+    return true;
+}
+static_assert(lds_pins_hold(), "objective_lds() moved: the layout of objective_lds.h no longer adds up to the pinned totals");
+}  // namespace
+// `slices`: copies of the per-peak records in a workgroup (1 when its waves are segments of one particle, else wpb);
+// `rows`: copies of the updated row kept for a fused swarm generation (0: none)
+size_t objective_lds(int variant, int32_t P, bool residual, int fit_im, int *variant_out, unsigned *aux_off, int wpb,
+                     int slices, int rows)
+{
+    const ResolvedLds r = resolve_lds(variant, P, residual, fit_im, wpb, slices, rows);
+    *variant_out = r.variant;
+    *aux_off = r.aux_off;
+    return r.lds;
 }
 
 int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, double *df, double *dR,
@@ -211,8 +249,7 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     int wpb = kWavesPerBlock, slices = 0, rows = 0;
     copies(wpb, &slices, &rows);
     size_t lds = objective_lds(ctx->variant, P, dR != nullptr, fit_im, &variant, &aux_off, wpb, slices, rows);
-    // (the context's own variant too: STAGED runs the DEFAULT kernel wherever the imaginary channel is on, and would
-    // answer here with DEFAULT's rows where include/nmrfit_amd_lsq_im.h promises a refusal)
+    // (the context's own variant too: a FARFIELD context whose records no longer fit resolves to DEFAULT above)
     if (rows_im && (variant != NMRFIT_VARIANT_DEFAULT || ctx->variant != NMRFIT_VARIANT_DEFAULT)) {
         set_error("residual rows with the imaginary channel exist for the DEFAULT kernel variant only (and while its LDS records fit)");
         return NMRFIT_E_UNSUPPORTED;

@@ -49,7 +49,7 @@ int launch_objective_norec(const ObjectiveLaunch &a);      // objective_norec.hi
 int launch_objective_farfield32(const ObjectiveLaunch &a); // objective_farfield32.hip (objective launches, fit_im = 0)
 int launch_objective_rows_im(const ObjectiveLaunch &a);   // objective_rows_im.hip (DEFAULT, residual rows of both channels)
 #ifdef NMRFIT_AB_BUILD
-int launch_objective_ab(int variant, const ObjectiveLaunch &a);   // objective_ab.hip: BASELINE, NOSKIP, SINGLE, QUAD, STAGED
+int launch_objective_ab(int variant, const ObjectiveLaunch &a);   // objective_ab.hip: BASELINE, NOSKIP
 #endif
 
 }  // namespace nmrfit

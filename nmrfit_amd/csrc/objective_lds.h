@@ -1,0 +1,46 @@
+// objective_lds.h -- the ONE description of the objective kernel's dynamic LDS.  objective_body (objective_kernel.h)
+// takes every pointer into it from objective_lds_layout, and objective_lds() (objective.hip) sizes the launch and picks
+// the fallback variant from the same function's `end`: a piece added here is added on both sides.
+//
+// The pieces, in order (byte offsets from the start of the dynamic LDS):
+//   lor    PeakLor[slices][P]        per-peak Lorentzian / Gaussian constants
+//   win    PeakWin[slices][P]        Gaussian windows                                     (then 16-byte alignment)
+//   seeds  double2[wpb][kMaxBlocks]  per-wave table of block seeds (<= 16 blocks per grid)
+//   shr    kSharedPrologueBytes      shared-prologue area: rotation step, lane seeds L_lane[64] re / im, one flag per wave
+//   lseed  double[wpb][2 * kWave]    per-wave lane seeds -- only when the waves hold different particles (slices != 1);
+//                                    a workgroup that is one particle keeps its one copy inside `shr`
+//   far    double[wpb][far_stride]   far-field / imaginary-sum scratch (FARFIELD, or fit_im == 2)
+//   grec   double2[slices][P]        (d, C) of the Gaussian recurrence (objective launches of DEFAULT / FARFIELD)
+//   lorf   PeakFast[slices][P]       scaled records of the two-operation pair form (DEFAULT)
+//   tab    kDawTabCount doubles      Dawson table (fit_im != 0), 16-byte aligned: the kernels' `aux_off`
+// `slices`: copies of the per-peak records in a workgroup -- 1 when its waves are segments of one particle, else wpb.
+#pragma once
+#include "objective_launch.h"
+#include "objective_math.h"
+
+namespace nmrfit {
+namespace {
+
+struct ObjectiveLds {
+    static constexpr size_t lor = 0;   // the first piece starts the area
+    size_t win, seeds, shr, lseed, far, grec, lorf, tab, end;
+};
+
+constexpr __host__ __device__ ObjectiveLds objective_lds_layout(int variant, bool residual, int fit_im, int P, int wpb, int slices)
+{
+    ObjectiveLds L{};
+    L.win = (size_t)slices * P * sizeof(PeakLor);
+    L.seeds = ((size_t)slices * P * (sizeof(PeakLor) + sizeof(PeakWin)) + 15) & ~(size_t)15;
+    L.shr = L.seeds + (size_t)wpb * kMaxBlocks * sizeof(double2);
+    L.lseed = L.shr + kSharedPrologueBytes;
+    L.far = L.lseed + (slices == 1 ? 0 : (size_t)wpb * 2 * kWave * sizeof(double));
+    L.grec = L.far + ((is_farfield(variant) || fit_im == 2) ? (size_t)wpb * far_stride(fit_im) * sizeof(double) : 0);
+    const bool rec = !residual && (variant == NMRFIT_VARIANT_DEFAULT || is_farfield(variant));
+    L.lorf = L.grec + (rec ? (size_t)slices * P * sizeof(double2) : 0);
+    L.tab = (L.lorf + (variant == NMRFIT_VARIANT_DEFAULT ? (size_t)slices * P * sizeof(PeakFast) : 0) + 15) & ~(size_t)15;
+    L.end = L.tab + (fit_im != 0 ? (size_t)kDawTabCount * sizeof(double) + 16 : 0);
+    return L;
+}
+
+}  // namespace
+}  // namespace nmrfit

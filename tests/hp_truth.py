@@ -129,7 +129,7 @@ def _ilogb(v):
 
 
 def kernel_forms(x, w, frame=None):
-    """Which forms the objective kernel's prologue (csrc/objective_kernel.h stage_peaks) picks for the particle x on
+    """Which forms the objective kernel's prologue (csrc/objective_prologue.h StagePeakConstants) picks for the particle x on
     the grid w, mirrored clause by clause in the same float64 operations.  Returns a dict:
 
         fast        every peak has 0 < al < 1e300 and, per aligned group of eight peaks, the sums of

@@ -241,9 +241,10 @@ def test_every_device_entry_point_reports_a_bad_device_index_alike():
 def test_variant_names():
     import pytest
     assert _cabi.variant_id("farfield") == _cabi.VARIANT_FARFIELD == 6
-    assert _cabi.variant_id("Default") == 0 and _cabi.variant_id(4) == _cabi.VARIANT_QUAD
-    with pytest.raises(ValueError):
-        _cabi.variant_id("fastest")
+    assert _cabi.variant_id("Default") == 0 and _cabi.variant_id(2) == _cabi.VARIANT_NOSKIP
+    for name in ("fastest", "quad", "single", "staged"):   # (the last three: retired A/B forms)
+        with pytest.raises(ValueError):
+            _cabi.variant_id(name)
     with pytest.raises(ValueError):
         _cabi.variant_id(9)
 

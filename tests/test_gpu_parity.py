@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 RTOL_F = 1e-9
 F_FLOOR = 1e-6
 # the kernels of the loaded library: DEFAULT / FARFIELD / NOREC in the product build; with NMRFIT_LIB pointing at the
-# A/B library (nmrfit_amd/csrc/build.sh --ab) also BASELINE, NOSKIP, SINGLE, QUAD, STAGED
+# A/B library (nmrfit_amd/csrc/build.sh --ab) also BASELINE, NOSKIP
 VARIANTS = _cabi.available_variants()
 HAS_AB = _cabi.has_ab_variants()
 # the plainest kernel at hand to check the tuned ones against: IEEE divide + libdevice exp2 per unit (A/B build), else
@@ -141,7 +141,7 @@ def test_empty_batch_and_errors(eq):
         with pytest.raises(ValueError):
             ev.objective_batch(np.zeros((2, 9)))          # 9 != 4 + 3P
         if HAS_AB:
-            ev.set_variant(_cabi.VARIANT_BASELINE)       # fit_im exists for DEFAULT / NOREC / FARFIELD (STAGED runs DEFAULT)
+            ev.set_variant(_cabi.VARIANT_BASELINE)       # fit_im exists for DEFAULT / NOREC / FARFIELD
             with pytest.raises(eq.NmrfitError) as ei:
                 ev.objective_batch(sp["x_true"][None, :], fit_im=True)
             assert ei.value.code == _cabi.E_UNSUPPORTED
@@ -257,7 +257,7 @@ def test_many_peaks(eq, P):
     X = synth.make_swarm(sp["lower"], sp["upper"], 9, seed=62, x_true=sp["x_true"])
     ref_R, ref_f = c_oracle.residual_batch(X, sp["w"], sp["u"], sp["v"], sp["weights"], threads=8)
     with eq.Evaluator(sp["w"], sp["u"], sp["v"], sp["weights"]) as ev:
-        for variant in [v for v in (_cabi.VARIANT_DEFAULT, _cabi.VARIANT_STAGED, _cabi.VARIANT_QUAD, _cabi.VARIANT_FARFIELD,
+        for variant in [v for v in (_cabi.VARIANT_DEFAULT, _cabi.VARIANT_NOSKIP, _cabi.VARIANT_BASELINE, _cabi.VARIANT_FARFIELD,
                                     _cabi.VARIANT_NOREC) if v in VARIANTS]:
             ev.set_variant(variant)
             _close_f(ev.objective_batch(X), ref_f)

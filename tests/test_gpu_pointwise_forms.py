@@ -2,7 +2,7 @@
 GPU tier: the objective kernel's two per-particle form switches, held to the high-precision truth one grid point at a
 time (tests/hp_truth.py; the one-hot probe of tests/test_gpu_pointwise.py).
 
-The prologue (objective_kernel.h stage_peaks) decides once per particle whether every Lorentzian group takes the
+The prologue (objective_prologue.h StagePeakConstants) decides once per particle whether every Lorentzian group takes the
 two-operation pair form with batch inversion (fast_all) and whether every Gaussian that touches a full chunk of a
 uniform grid is evaluated by recurrence from the lane's first row (rec_all).  One peak decides for the whole particle.
 hp_truth.kernel_forms mirrors the two predicates in Python; every particle here is ASSERTED to be in its intended

@@ -841,7 +841,7 @@ def test_deferred_fold_survives_a_change_of_kernel_between_generations():
         dev.init()
         dev.step()
         if _cabi.has_ab_variants():
-            walk = (("default", False, 1), ("quad", False, 3), ("default", False, 1), ("single", False, 3), ("farfield", False, 1))
+            walk = (("default", False, 1), ("noskip", False, 3), ("default", False, 1), ("baseline", False, 3), ("farfield", False, 1))
         else:   # (3: objective, posts, final reduction -- the default hand-over is TWO_LAUNCH since round 5)
             walk = (("default", False, 1), ("default", True, 3), ("default", False, 1), ("norec", "sum", 3), ("farfield", False, 1))
         for variant, fit_im, launches in walk:
@@ -928,7 +928,7 @@ def test_random_walk_over_the_swarm_interface_matches_the_mirror(seed):
             elif op == 12:
                 dev.set_handover(str(rng.choice(["fast", "fenced", "two_launch"])))
             elif op == 13:                    # another kernel for the generations that follow (the mirror evaluates through the same context)
-                ev.set_variant(_cabi.variant_id(str(rng.choice(["default", "farfield", "norec", "quad", "staged"] if _cabi.has_ab_variants()
+                ev.set_variant(_cabi.variant_id(str(rng.choice(["default", "farfield", "norec", "noskip", "baseline"] if _cabi.has_ab_variants()
                                                                   else ["default", "farfield", "norec", "norec", "default"]))))
         check_all("the end (%s)" % log[-12:])
         if seed == 2:

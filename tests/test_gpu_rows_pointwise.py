@@ -90,8 +90,7 @@ def check_stack(ev, X, points, wt, zeros, worst, tag):
         R = ev.residual_batch(X)
         read(R, "re", var)
         rows[var] = R
-        # both channels: the DEFAULT kernel alone (STAGED of an A/B build included, whose objective launches run the
-        # DEFAULT kernel wherever the imaginary channel is on: up to this test it answered with DEFAULT's rows)
+        # both channels: the DEFAULT kernel alone (every other variant of the context is refused)
         if var != _cabi.VARIANT_DEFAULT:
             refused(ev, X)
             np.testing.assert_array_equal(ev.residual_batch(X), R, err_msg="after the refusal: %s" % (tag + (var,),))

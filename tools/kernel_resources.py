@@ -16,7 +16,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nmrfit_amd", "csrc")
-VARIANTS = {0: "DEFAULT", 1: "BASELINE", 2: "NOSKIP", 3: "SINGLE", 4: "QUAD", 5: "STAGED", 6: "FARFIELD", 7: "NOREC", 8: "FARFIELD32"}
+VARIANTS = {0: "DEFAULT", 1: "BASELINE", 2: "NOSKIP", 6: "FARFIELD", 7: "NOREC", 8: "FARFIELD32"}
 
 
 def demangle(names):
