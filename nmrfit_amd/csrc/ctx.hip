@@ -98,6 +98,7 @@ int nmrfit_ctx_create(int device, int64_t N, const double *w, const double *u, c
     ctx->n_chunks = block_plan(N).n_chunks;
     if (const char *tw = getenv("NMRFIT_TARGET_WAVES")) ctx->target_waves = atoll(tw);   // tuning knob
     if (getenv("NMRFIT_NO_WIDE_WORKGROUPS")) ctx->wide_workgroups = false;               // A/B knob
+    if (const char *pw = getenv("NMRFIT_PAIR_WAVES")) ctx->pair_waves = atoi(pw) != 0 ? 1 : 0;   // A/B knob
     // test knob: run a whole test suite with another kernel variant as every context's default
     if (const char *dv = getenv("NMRFIT_DEFAULT_VARIANT")) {
         const int vnum = atoi(dv);

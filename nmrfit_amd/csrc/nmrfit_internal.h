@@ -141,6 +141,7 @@ struct nmrfit_ctx {
     double grid_dev = 0.0;       // bound on |(w[j+k] - w[j]) - k*spacing| over the grid (Gaussian recurrence)
     int64_t target_waves = 0;    // launch-geometry override (0 = heuristic)
     bool wide_workgroups = true; // eight-wave workgroups for particles cut into eight segments (NMRFIT_NO_WIDE_WORKGROUPS: A/B knob)
+    int pair_waves = -1;         // the objective kernel's pair form: -1 where its pairs fill the chip, 0 never, 1 wherever the geometry allows (NMRFIT_PAIR_WAVES: A/B knob)
     void *d_block = nullptr;     // the one allocation behind d_wc, d_u, d_v, d_wt, d_chunk, d_stage
     double *d_wc = nullptr;      // centred grid
     double *d_u = nullptr, *d_v = nullptr, *d_wt = nullptr;

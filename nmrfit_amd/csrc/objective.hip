@@ -1,7 +1,8 @@
 // objective.hip -- host side of the hot path: launch geometry (segments per particle, waves per workgroup), the LDS
 // budget that picks the kernel form, and the launch itself (launch_objective); plus the small kernels around it
 // (block-sum finalisation, grid preparation; the post-fit reconstruction is result.hip).  The objective kernel is
-// objective_kernel.h; its instantiations live in objective_{default,farfield,norec}.hip.
+// objective_kernel.h; its instantiations live in objective_{default,farfield,norec}.hip, the DEFAULT kernel's pair form
+// (two particles per workgroup) in objective_pair.h / objective_pair.hip.
 #include "objective_launch.h"
 #include "objective_lds.h"
 #include "objective_math.h"
@@ -271,12 +272,28 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
             aux_off = aux8;
         }
     }
-    const int64_t blocks = (waves + wpb - 1) / wpb;
+    // The pair form (objective_pair.h): a four-wave workgroup is TWO particles cut into four segments, and a wave fetches
+    // every chunk of the grid once for both.  For objective launches of the DEFAULT kernel whose pairs still fill the
+    // chip's four-waves-per-SIMD slots once (smaller swarms keep a workgroup per particle: more of them to spread);
+    // NMRFIT_PAIR_WAVES=0 / 1: never / wherever the geometry allows (A/B knob, nmrfit_ctx::pair_waves).
+    bool pair = false;
+    if (variant == NMRFIT_VARIANT_DEFAULT && !dR && fit_im == 0 && nseg == kWavesPerBlock && wpb == kWavesPerBlock &&
+        ctx->pair_waves != 0 && (ctx->pair_waves > 0 || (S / 2) * kWavesPerBlock >= (int64_t)ctx->compute_units * 4 * 4)) {
+        const size_t lds2 = objective_pair_lds_layout(P > 1 ? P : 1).end;
+        if (lds2 + kPairStaticLds + 16 + (size_t)kPairParticles * rows * xrow_bytes <= 160 * 1024) {
+            pair = true;
+            lds = lds2;
+            rows *= kPairParticles;
+            aux_off = 0;
+        }
+    }
+    const size_t static_lds = pair ? kPairStaticLds : kStaticLds;
+    const int64_t blocks = pair ? (S + 1) / 2 : (waves + wpb - 1) / wpb;
     if (blocks > 0x7fffffffLL) {
         set_error("swarm too large for one launch");
         return NMRFIT_E_INVALID;
     }
-    if (lds + kStaticLds + 16 + (size_t)rows * xrow_bytes > 160 * 1024) {
+    if (lds + static_lds + 16 + (size_t)rows * xrow_bytes > 160 * 1024) {
         set_error("too many peaks for the kernel's LDS records (with the imaginary model / the fused swarm update)");
         return NMRFIT_E_UNSUPPORTED;
     }
@@ -332,6 +349,7 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
     la.upd = upd;
     la.aux_off = aux_off;
     la.wpb = wpb;
+    la.pair = pair;
     int rc;
     if (rows_im) {
         rc = launch_objective_rows_im(la);
@@ -348,7 +366,7 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
         return NMRFIT_OK;
     }
     switch (variant) {   // one translation unit per selectable variant (they compile in parallel)
-        case NMRFIT_VARIANT_DEFAULT: rc = launch_objective_default(la); break;
+        case NMRFIT_VARIANT_DEFAULT: rc = pair ? launch_objective_pair(la) : launch_objective_default(la); break;
         case NMRFIT_VARIANT_FARFIELD: rc = launch_objective_farfield(la); break;
         case NMRFIT_VARIANT_FARFIELD32: rc = launch_objective_farfield32(la); break;
         case NMRFIT_VARIANT_NOREC: rc = launch_objective_norec(la); break;
@@ -374,7 +392,7 @@ int launch_objective(nmrfit_ctx *ctx, int64_t S, int32_t P, const double *dX, do
                            ctx->d_partial, S, n_blocks, N, fit_im, df);
         NMRFIT_HIP(hipGetLastError());
     }
-    ctx->last.waves = waves;
+    ctx->last.waves = pair ? blocks * wpb : waves;   // (the pair form: a wave holds a segment of two particles)
     ctx->last.waves_per_workgroup = wpb;
     ctx->last.nseg = (int32_t)nseg;
     ctx->last.seg_len = seg_len;

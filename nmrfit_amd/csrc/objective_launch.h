@@ -24,6 +24,7 @@ struct ObjectiveLaunch {
     PsoFused upd;
     unsigned aux_off;
     int wpb;               // waves per workgroup (4, or 8: has_eight_wave_form)
+    bool pair;             // the pair form: a workgroup is two particles (objective_pair.h); `blocks` counts pairs
 };
 
 // Which instantiations exist with eight-wave workgroups (one workgroup = one particle cut into eight segments):
@@ -48,6 +49,7 @@ int launch_objective_farfield(const ObjectiveLaunch &a);   // objective_farfield
 int launch_objective_norec(const ObjectiveLaunch &a);      // objective_norec.hip
 int launch_objective_farfield32(const ObjectiveLaunch &a); // objective_farfield32.hip (objective launches, fit_im = 0)
 int launch_objective_rows_im(const ObjectiveLaunch &a);   // objective_rows_im.hip (DEFAULT, residual rows of both channels)
+int launch_objective_pair(const ObjectiveLaunch &a);      // objective_pair.hip (DEFAULT, objective launches, two particles per workgroup)
 #ifdef NMRFIT_AB_BUILD
 int launch_objective_ab(int variant, const ObjectiveLaunch &a);   // objective_ab.hip: BASELINE, NOSKIP
 #endif

@@ -42,5 +42,46 @@ constexpr __host__ __device__ ObjectiveLds objective_lds_layout(int variant, boo
     return L;
 }
 
+// The pair form (objective_pair.h: a four-wave workgroup is TWO particles, wave s holds segment s of both).  Its pieces:
+//   lor    PeakLor[2][P]             the records of particle A, then of particle B -- like every piece with a [2]
+//   lorf   PeakFast[2][P]
+//   grec   double2[2][P]
+//   win    PeakWin[2][P]                                                                  (then 16-byte alignment)
+//   seeds  double2[2][4][kMaxBlocks] per-wave tables of block seeds
+//   shr    [2] kSharedPrologueBytes  rotation step, lane seeds, one flag per wave
+//   park   f64x2[4][4][kWave]        per wave: A's eight accumulators while B's model runs, [16-byte piece][lane]
+//                                    (a lane's ds_*_b128 accesses of one piece are consecutive: conflict-free)
+//   state  double[4][2][3][kWave]    per wave and particle: the phase recurrence (re, im) and the block's sum of squares
+//                                    of every lane, between the particle's epilogues
+struct ObjectivePairLds {
+    static constexpr size_t lor = 0;
+    size_t lorf, grec, win, seeds, shr, park, state, end;
+};
+constexpr int kPairParticles = 2;
+constexpr size_t kPairParkBytes = (size_t)kPointsPerLane * sizeof(double) * kWave;   // per wave
+constexpr size_t kPairStateBytes = (size_t)kPairParticles * 3 * sizeof(double) * kWave;   // per wave
+
+constexpr __host__ __device__ ObjectivePairLds objective_pair_lds_layout(int P)
+{
+    ObjectivePairLds L{};
+    const size_t n = (size_t)kPairParticles * P;
+    L.lorf = n * sizeof(PeakLor);
+    L.grec = L.lorf + n * sizeof(PeakFast);
+    L.win = L.grec + n * sizeof(double2);
+    L.seeds = (L.win + n * sizeof(PeakWin) + 15) & ~(size_t)15;
+    L.shr = L.seeds + (size_t)kPairParticles * kWavesPerBlock * kMaxBlocks * sizeof(double2);
+    L.park = L.shr + (size_t)kPairParticles * kSharedPrologueBytes;
+    L.state = L.park + (size_t)kWavesPerBlock * kPairParkBytes;
+    L.end = L.state + (size_t)kWavesPerBlock * kPairStateBytes;
+    return L;
+}
+// the pair kernel's own __shared__: one wsums block per particle (+ alignment slack)
+constexpr size_t kPairStaticLds = (size_t)kPairParticles * kWsumsCount * sizeof(double) + 64;
+// Four workgroups per CU at the headline shape: records of 24 peaks, one fused row per particle, static LDS -- within a
+// quarter of the CU's 160 KiB
+static_assert(kSharedPrologueBytes % 16 == 0 && sizeof(PeakLor) % 16 == 0 && sizeof(PeakFast) % 16 == 0, "16-byte pieces");
+static_assert(objective_pair_lds_layout(24).end + 16 + (size_t)kPairParticles * (4 + 3 * 24) * sizeof(double) + kPairStaticLds <= 40 * 1024,
+              "pair form: four workgroups no longer fit on a CU at P = 24");
+
 }  // namespace
 }  // namespace nmrfit

@@ -4,9 +4,10 @@ remarks (no GPU needed): compiles each .hip of nmrfit_amd/csrc for gfx950 with
 -Rpass-analysis=kernel-resource-usage and prints one line per kernel.  Spills show up as a
 non-zero `scratch` column; `tools/kernel_resources.py --check` exits 1 if any objective_kernel
 instantiation that nmrfit_amd.fit() can select (variants DEFAULT / FARFIELD / NOREC, with or without
-the imaginary channel, plus every residual form) uses scratch memory.
+the imaginary channel, plus every residual form) uses scratch memory, or if the pair form of the DEFAULT objective
+kernel (objective_pair.hip) leaves its budget: at most 128 VGPRs, no scratch, four waves per SIMD.
 
-    python tools/kernel_resources.py [--check] [extra hipcc flags, e.g. -DNMRFIT_POINTS=4]
+    python tools/kernel_resources.py [--check] [--unit objective_pair.hip ...] [extra hipcc flags, e.g. -DNMRFIT_POINTS=4]
 """
 import os
 import re
@@ -24,10 +25,10 @@ def demangle(names):
     return [re.sub(r"\(.*", "", o.replace("nmrfit::(anonymous namespace)::", "").replace("void ", "")) for o in out]
 
 
-def resources(extra):
+def resources(extra, units=()):
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in ("objective_default.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip"):
+        for src in units or ("objective_default.hip", "objective_pair.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip"):
             if not os.path.exists(os.path.join(CSRC, src)):
                 continue
             cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
@@ -53,8 +54,14 @@ def resources(extra):
 
 def main():
     check = "--check" in sys.argv
-    extra = [a for a in sys.argv[1:] if a != "--check"]
-    rows = resources(extra)
+    args = [a for a in sys.argv[1:] if a != "--check"]
+    units = []
+    while "--unit" in args:   # only these translation units
+        i = args.index("--unit")
+        units.append(args[i + 1])
+        del args[i:i + 2]
+    extra = args
+    rows = resources(extra, tuple(units))
     bad = []
     print("%-58s %5s %5s %8s %6s %8s %8s" % ("kernel", "VGPR", "AGPR", "scratch", "waves", "LDS", "s-spill"))
     for r in rows:
@@ -72,6 +79,9 @@ def main():
             label = "objective_batch_kernel<%s,%s%s>" % (VARIANTS.get(int(mb.group(1)), mb.group(1)),
                                                          "wave=particle" if mb.group(3) == "true" else "%s waves" % mb.group(2),
                                                          ",fit_im=%s" % mb.group(4) if mb.group(4) != "0" else "")
+        pair = re.match(r"objective_kernel_pair<\d+>", name) is not None
+        if pair:
+            label = "objective_kernel_pair<DEFAULT,objective,fit_im=0>"
         scratch = int(r.get("ScratchSize [bytes/lane]", "0"))
         # (s-spill: scalar registers parked in VGPR lanes -- v_writelane / v_readlane, which are VALU instructions: in a
         # loop they cost issue slots like arithmetic does)
@@ -80,8 +90,11 @@ def main():
                                                 r.get("SGPRs Spill", "?")))
         if selectable and scratch:
             bad.append(label)
+        # the pair form pays only while it runs four waves per SIMD
+        if pair and (scratch or int(r.get("VGPRs", "999")) > 128 or int(r.get("Occupancy [waves/SIMD]", "0")) < 4):
+            bad.append(label)
     if check and bad:
-        print("SPILLS in kernels fit() can select:", bad)
+        print("SPILLS in kernels fit() can select (or the pair form outside 128 VGPRs / four waves):", bad)
         return 1
     return 0
 
