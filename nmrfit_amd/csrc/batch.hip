@@ -220,7 +220,7 @@ void plan_geometry(BatchPart *b)
         if (v != b->variant) continue;   // (would run another kernel than a lone fit: not bit-identical)
         lds = (lds + 15) & ~(size_t)15;   // the row copies come last (their offset, xrow_offset below, travels in the
         lds += row_copy_bytes(g.wave_swarm, b->Pmax);   // descriptor tables: PsoFused::xrow_off, re-stamped when the geometry changes)
-        if (lds + kObjectiveStaticLds + 16 > 160 * 1024) continue;
+        if (!lds_fits(lds, kObjectiveStaticLds)) continue;
         g.lds = lds;
         g.aux_off = aux;
         b->geom_ok[m] = true;

@@ -194,7 +194,7 @@ bool rows_batch_lds(int32_t Pmax, int fit_im, size_t *lds, unsigned *aux_off)
 {
     int v = NMRFIT_VARIANT_DEFAULT;
     *lds = objective_lds(NMRFIT_VARIANT_DEFAULT, Pmax, true, fit_im, &v, aux_off, kWavesPerBlock, kWavesPerBlock, 0);
-    return v == NMRFIT_VARIANT_DEFAULT && *lds + kObjectiveStaticLds + 16 <= 160 * 1024;
+    return v == NMRFIT_VARIANT_DEFAULT && lds_fits(*lds, kObjectiveStaticLds);
 }
 
 int launch_rows_batch(hipStream_t st, const RowsFit *d_fits, int32_t K, int64_t Smax, size_t lds, unsigned aux_off, int fit_im)

@@ -28,9 +28,9 @@ struct BlockPlan {
     int64_t n_blocks;    // blocks per grid (<= kMaxBlocks)
     int64_t blk_len;     // points per block
 };
-inline BlockPlan block_plan(int64_t N)
+constexpr BlockPlan block_plan(int64_t N)
 {
-    BlockPlan p;
+    BlockPlan p{};
     p.n_chunks = (N + kChunk - 1) / kChunk;
     p.blk_chunks = (int)((p.n_chunks + kMaxBlocks - 1) / kMaxBlocks);
     p.n_blocks = (p.n_chunks + p.blk_chunks - 1) / p.blk_chunks;

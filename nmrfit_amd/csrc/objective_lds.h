@@ -1,5 +1,5 @@
 // objective_lds.h -- the ONE description of the objective kernel's dynamic LDS.  objective_body (objective_kernel.h)
-// takes every pointer into it from objective_lds_layout, and objective_lds() (objective.hip) sizes the launch and picks
+// takes every pointer into it from objective_lds_layout, and resolve_lds (objective_plan.h) sizes the launch and picks
 // the fallback variant from the same function's `end`: a piece added here is added on both sides.
 //
 // The pieces, in order (byte offsets from the start of the dynamic LDS):
