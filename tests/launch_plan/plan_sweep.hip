@@ -119,6 +119,10 @@ void check_launch(const ObjectivePlanInput &in, const sweep::Mode &m, const Obje
     HOLDS(!p.tail || (p.pbest && S <= (int64_t)kDeferredPerLane * 64 * p.wpb));
     HOLDS(!in.fused_rows || (p.xrow_off % 16 == 0 && ((int64_t)p.lds - (int64_t)p.xrow_off) % row_bytes == 0 &&
                              (int64_t)p.lds - (int64_t)p.xrow_off == p.rows * row_bytes));
+    // the row copies the kernels count on without being told: swarm_prologue / personal_best of a workgroup that is one
+    // particle, and objective_pair_body (B's rows start `rows per particle` rows behind A's), derive them from the tail flag
+    HOLDS(!(in.fused_rows && !p.pair && p.nseg == p.wpb) || p.rows == (p.tail ? 3 : 1));
+    HOLDS(!(in.fused_rows && p.pair) || p.rows == 2 * (p.tail ? 3 : 1));
     HOLDS(p.unit != kUnitFarfield32 || (!in.residual && p.fit_im == 0));
     HOLDS((p.partial_doubles != 0) == (p.nseg != 1 && p.nseg != p.wpb) && p.direct_f == (p.partial_doubles == 0));
     HOLDS(!in.pending || p.tail);

@@ -14,7 +14,13 @@ they return with np.array_equal.  The shapes are the smallest on which the pair 
     amplitude (2), a group outside the scaled form's exponent budget (3), a peak on a chunk boundary (4) -- ordered so that
     (scaled, general) and (general, scaled) pairs occur, and pairs of a broad-lined particle (recurrence) with a
     narrow-lined one (none) in both orders.
-Then the whole state of 5- and 8-particle swarms after three fused generations, one of them stopped by the second.
+Then the whole state of 5- and 8-particle swarms after three fused generations, one of them stopped by the second.  At that
+size the whole generation rides in the launch: this is the DEFERRED-FOLD mode (three row copies per particle, six per
+workgroup, personal bests written through pflip), which the plan reaches only with NMRFIT_PAIR_WAVES=1 -- left alone it
+takes the pair form from S = 8 x compute units on, beyond the 1024 particles of the deferred fold.  The modes the pair form
+runs in by itself (personal best in the launch with the fold in the select kernel, personal best outside the launch, the
+rank protocol, shards at odd offsets, up to 739 peaks, the plan's own choice, a change of kernel under a waiting fold) are
+held in tests/test_gpu_pair_swarm_modes.py, which uses this file's helpers.
 """
 import contextlib
 import importlib.util

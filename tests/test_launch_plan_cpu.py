@@ -8,7 +8,7 @@ tests/golden/launch_plan_parent.txt, were recorded from launch_objective itself 
 (profiles/r12/launch_objective_record.hip: the function with its kernel units, workspace and launches replaced by
 recorders).  The program also checks the invariants of every planned launch (LDS within the CU's 160 KiB, segments
 that tile the grid in whole blocks, when a workgroup may be wide or a pair, where f goes, what of a swarm generation
-rides along) and fails on the first violation.  No HIP call: hipcc compiles it, nothing needs a GPU.
+rides along and how many copies of a fused row a workgroup keeps for it) and fails on the first violation.  No HIP call: hipcc compiles it, nothing needs a GPU.
 """
 import os
 import re
