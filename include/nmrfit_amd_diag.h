@@ -121,7 +121,8 @@ int nmrfit_batch_step(nmrfit_batch *batch);
 int nmrfit_batch_synchronize(nmrfit_batch *batch);
 /* launch geometry: 0 workgroup = particle (4 or 8 waves: the particle's grid segments, what a lone default fit uses),
  * 1 wave = particle (one segment; the wave does the particle's whole step).  Chosen at creation from K x swarmsize;
- * NMRFIT_E_UNSUPPORTED where the shape does not allow the form.  Results are bit-identical either way. */
+ * NMRFIT_E_UNSUPPORTED where the shape does not allow the form -- of ANY part of the batch: the call is all or nothing, a
+ * refused call has changed no part.  Results are bit-identical either way. */
 int nmrfit_batch_set_geometry(nmrfit_batch *batch, int mode);
 int nmrfit_batch_geometry(const nmrfit_batch *batch, int32_t *mode, int32_t *waves_per_workgroup, int32_t *segments,
                           int64_t *workgroups);

@@ -43,6 +43,11 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
     ``nmrfit.fit``, nmrfit/core.py:64; its only parallel mode spreads ONE fit's particles over processes,
     nmrfit/utils.py:182).  ``summary`` defaults to False here.
 
+    Shared and per-job arguments: a job's own entries win over the call's keyword arguments; ``options`` are merged key
+    by key -- the call's ``options`` first, the job's own keys over them -- and that is the rule on every routing below
+    (one device, ``devices=[...]``, ``shard=True``): ``fit_many(jobs_with_their_own_seed, options={"maxiter": 5})`` runs
+    5 generations of every job wherever it lands.
+
     How the jobs run:
 
     * ``batch=True`` (default): jobs of equal kernel variant, ``fit_im``, ``maxiter`` and ``check_every`` -- grid lengths,
@@ -141,13 +146,27 @@ def _result_record(f):
     return dict(params=list(map(float, f.params)), error=float(f.error), seed=getattr(f, "seed", None))
 
 
-def _with_device(job, shared_options, device, force=False):
-    """The job with ``device`` in ITS OWN options: a job's ``options`` dict replaces the shared one when the two are
-    merged (dict(kwargs, **job)), so a device that only sits in the shared options is lost for every job that brings a
-    seed or a maxiter.  ``force``: the caller assigns the device (devices=[...]); otherwise a device the job or the
-    shared options name wins."""
-    opts = dict(shared_options)
+def _merged_options(shared_options, job):
+    """The ``options`` one job is fitted with, on every routing: the call's shared options first, the job's own keys
+    win."""
+    opts = dict(shared_options or {})
     opts.update(job.get("options") or {})
+    return opts
+
+
+def _fit_args(call, job):
+    """``fit``'s arguments for one job: the call's keyword arguments, the job's own entries over them -- except
+    ``options``, which are merged key by key (``_merged_options``)."""
+    args = dict(call.kwargs, **job)
+    if "options" in call.kwargs or "options" in job:
+        args["options"] = _merged_options(call.kwargs.get("options"), job)
+    return args
+
+
+def _with_device(job, shared_options, device, force=False):
+    """The job with ``device`` in its own (merged) options.  ``force``: the caller assigns the device
+    (devices=[...]); otherwise a device the job or the shared options name wins."""
+    opts = _merged_options(shared_options, job)
     if force or opts.get("device") is None:
         opts["device"] = device
     return dict(job, options=opts)
@@ -190,7 +209,7 @@ def _fit_many_sharded(jobs, call, rank, world, channel=None, local=None):
             continue
         for i, rec in json.loads(blob.decode()):
             job = jobs[i]
-            args = {k: v for k, v in dict(call.kwargs, **job).items() if k not in ("data", "lower", "upper")}
+            args = {k: v for k, v in _fit_args(call, job).items() if k not in ("data", "lower", "upper")}
             f = utils.FitUtility(job["data"], job["lower"], job["upper"], **args)
             f.params, f.error, f.seed = np.array(rec["params"]), rec["error"], rec["seed"]
             out[i] = f
@@ -443,7 +462,7 @@ class _Pipeline:
 def _fit_many_local(jobs, call):
     fits = []
     for job in jobs:
-        args = dict(call.kwargs, **job)
+        args = _fit_args(call, job)
         fits.append(utils.FitUtility(args.pop("data"), args.pop("lower"), args.pop("upper"), **args))
     if not (call.batch and len(fits) > 1):
         return _fit_alone(fits, {}, range(len(fits)), call)

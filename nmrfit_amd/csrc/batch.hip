@@ -388,14 +388,22 @@ static int part_best(BatchPart *b, double *x_best, double *f_best)
 }
 
 
+static bool part_allows_geometry(const BatchPart *b, int mode)
+{
+    return mode >= 0 && mode <= 1 && b->geom_ok[mode];
+}
+
+static int refuse_geometry()
+{
+    set_error("nmrfit_batch_set_geometry: 0 (workgroup = particle) or 1 (wave = particle), where the shape allows it");
+    return NMRFIT_E_UNSUPPORTED;
+}
+
 static int part_set_geometry(BatchPart *b, int mode)
 {
     int rc = bind_batch(b);
     if (rc != NMRFIT_OK) return rc;
-    if (mode < 0 || mode > 1 || !b->geom_ok[mode]) {
-        set_error("nmrfit_batch_set_geometry: 0 (workgroup = particle) or 1 (wave = particle), where the shape allows it");
-        return NMRFIT_E_UNSUPPORTED;
-    }
+    if (!part_allows_geometry(b, mode)) return refuse_geometry();
     if (mode == b->mode) return NMRFIT_OK;
     if ((rc = flush_fold(b)) != NMRFIT_OK) return rc;
     NMRFIT_HIP(hipStreamSynchronize(b->stream));
@@ -519,6 +527,10 @@ int nmrfit_batch_best(nmrfit_batch *b, double *x_best, double *f_best)
 int nmrfit_batch_set_geometry(nmrfit_batch *b, int mode)
 {
     int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    // all or nothing: a form that one part's shapes do not allow is refused before any part has changed
+    for (const BatchPart *q : b->parts)
+        if (!part_allows_geometry(q, mode)) return refuse_geometry();
     for (size_t p = 0; rc == NMRFIT_OK && p < b->parts.size(); ++p) rc = part_set_geometry(b->parts[p], mode);
     return rc;
 }

@@ -307,6 +307,46 @@ def test_the_rank_device_reaches_jobs_that_bring_their_own_options(monkeypatch):
     assert got == [(4, 1), (5, None)]
 
 
+def test_shared_options_mean_the_same_on_every_routing(monkeypatch):
+    """One rule for fit_many's shared ``options``: the call's first, the job's own keys win -- whichever way the jobs
+    reach a batch.  The FitUtility objects of the local call, of devices=[0] and of the sharded path carry the same
+    options apart from ``device``: a job with its own seed and maxiter, one with its own seed only, one with none."""
+    def fake_fit(self, plan=None):
+        self.params, self.error = np.zeros(len(self.lower)), 0.0
+    monkeypatch.setattr(utils.FitUtility, "fit", fake_fit)
+    monkeypatch.setattr(core, "_cabi_device_count", lambda: 1)
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("LOCAL_RANK", "0")
+    monkeypatch.setenv("RANK", "0")
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    shared = {"maxiter": 5, "swarmsize": 16, "tag": "shared"}
+
+    def jobs():
+        return [_job(512, 2, 30, options={"seed": 1, "maxiter": 9}), _job(512, 2, 31, options={"seed": 2}), _job(512, 2, 32)]
+
+    class Chan:
+        def all_gather(self, blob):
+            return [blob]
+
+        def close(self):
+            pass
+    local = core.fit_many(jobs(), batch=False, options=shared)
+    listed = core.fit_many(jobs(), batch=False, devices=[0], options=shared)
+    sharded = core._fit_many_sharded(jobs(), core._Call(1, False, dict(summary=False, options=shared), False, False, False),
+                                     0, 1, channel=Chan())
+    want = [dict(shared, seed=1, maxiter=9), dict(shared, seed=2), dict(shared)]
+    for name, fits in (("local", local), ("devices", listed), ("sharded", sharded)):
+        got = [{k: v for k, v in f.options.items() if k != "device"} for f in fits]
+        assert got == want, name
+    assert [f.options.get("device") for f in listed] == [0, 0, 0] and [f.options.get("device") for f in sharded] == [0, 0, 0]
+    assert all("device" not in f.options for f in local)
+    assert shared == {"maxiter": 5, "swarmsize": 16, "tag": "shared"}             # (the caller's dict is not written to)
+    # a call without shared options leaves the jobs' own as they are, and a job without any gets none
+    plain = core.fit_many(jobs(), batch=False)
+    assert [f.options for f in plain[:2]] == [{"seed": 1, "maxiter": 9}, {"seed": 2}] and not plain[2].options
+
+
 def test_batch_size_rule():
     """Jobs per device batch: a quarter of the list, between 40 and 200 (profiles/r06/fit_many_span_sweep.txt); a number in
     core.BATCH_JOBS overrides."""

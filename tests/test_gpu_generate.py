@@ -15,34 +15,13 @@ import pytest
 from nmrfit_amd import proc_autophase, synth, utils
 from nmrfit_amd.batch import FitBatch
 from nmrfit_amd.equations import Evaluator
+from tests.batch_walk_support import lone_result as _lone_result, same_result as _same_result
 
 pytestmark = pytest.mark.gpu
-
-_ATTRS = ("u", "v", "V", "I", "w")
 
 
 def _problems(K, N=4096, peaks=(6, 4, 9, 1, 7, 6, 12, 3), seed0=140):
     return [synth.make_spectrum(N, peaks[k % len(peaks)], seed=seed0 + k, physical=True) for k in range(K)]
-
-
-def _lone_result(sp, x, scale):
-    data = synth.SynthData(sp["w"], sp["u"], sp["v"], sp["peaks"])
-    fu = utils.FitUtility(data, sp["lower"], sp["upper"], summary=False)
-    fu.params = x
-    fu.generate_result(scale)
-    return fu, data
-
-
-def _same_result(a, b, data_a, data_b, tag):
-    for name in _ATTRS:
-        np.testing.assert_array_equal(getattr(a, name), getattr(b, name), err_msg="%s %s" % (tag, name))
-    assert len(a.real_contribs) == len(b.real_contribs) == len(a.imag_contribs)
-    for k in range(len(a.real_contribs)):
-        np.testing.assert_array_equal(a.real_contribs[k], b.real_contribs[k], err_msg="%s real %d" % (tag, k))
-        np.testing.assert_array_equal(a.imag_contribs[k], b.imag_contribs[k], err_msg="%s imag %d" % (tag, k))
-    np.testing.assert_array_equal(data_a.V, data_b.V, err_msg=tag)
-    np.testing.assert_array_equal(data_a.I, data_b.I, err_msg=tag)
-    assert data_a.p0 == data_b.p0 and data_a.p1 == data_b.p1
 
 
 def test_lone_generate_result_against_the_numpy_restatement():
