@@ -101,7 +101,9 @@ int nmrfit_pso_set_fused_pbest(nmrfit_pso *pso, int enable);
 int nmrfit_pso_set_fused_tail(nmrfit_pso *pso, int enable);
 int nmrfit_pso_last_launches(const nmrfit_pso *pso, int32_t *launches);
 /* copy swarm state to host for inspection/tests (any pointer may be NULL):
- * x, v, p are S_local x D; fx, fp are S_local */
+ * x, v, p are S_local x D; fx, fp are S_local.  NMRFIT_E_STATE before nmrfit_pso_init, like nmrfit_pso_candidate_dev:
+ * generation 0 is the first writer of these arrays.  (nmrfit_pso_status and nmrfit_pso_best are defined from creation
+ * on: 0 generations, not stopped, fg = best_f = 0, best_x = 0.) */
 int nmrfit_pso_get_state(nmrfit_pso *pso, double *x, double *v, double *p, double *fx, double *fp);
 
 /* ---- communicator bookkeeping ------------------------------------------------------------------------------------- */
@@ -126,7 +128,8 @@ int nmrfit_batch_synchronize(nmrfit_batch *batch);
 int nmrfit_batch_set_geometry(nmrfit_batch *batch, int mode);
 int nmrfit_batch_geometry(const nmrfit_batch *batch, int32_t *mode, int32_t *waves_per_workgroup, int32_t *segments,
                           int64_t *workgroups);
-/* swarm state of fit k (any pointer may be NULL): x, v, p are S x (4 + 3 P[k]); fx, fp are S */
+/* swarm state of fit k (any pointer may be NULL): x, v, p are S x (4 + 3 P[k]); fx, fp are S.  NMRFIT_E_STATE before
+ * the first generation, like nmrfit_batch_status and nmrfit_batch_best. */
 int nmrfit_batch_get_state(nmrfit_batch *batch, int32_t k, double *x, double *v, double *p, double *fx, double *fp);
 
 /* ---- automatic phase correction: the optimiser alone ---------------------------------------------------------------

@@ -440,8 +440,8 @@ static int part_get_state(BatchPart *b, int32_t k, double *x, double *v, double 
 {
     int rc = bind_batch(b);
     if (rc != NMRFIT_OK) return rc;
-    if (k < 0 || k >= b->K || !b->initialized)
-        return refuse(NMRFIT_E_INVALID, "nmrfit_batch_get_state: fit index out of range, or before the first generation");
+    if (k < 0 || k >= b->K) return refuse(NMRFIT_E_INVALID, "nmrfit_batch_get_state: fit index out of range");
+    if (!b->initialized) return refuse(NMRFIT_E_STATE, "nmrfit_batch_get_state before the first generation");
     if ((rc = flush_fold(b)) != NMRFIT_OK) return rc;
     BatchFit f;
     NMRFIT_HIP(hipMemcpy(&f, table(b, b->xp + 2 * b->b) + k, sizeof f, hipMemcpyDeviceToHost));

@@ -305,7 +305,7 @@ int part_create(int device, int32_t K, const int64_t *Nk, const double *w, const
     std::vector<int32_t> region_spec;
     if (!weights) weights_layout(K, Nk, R, &wspecs, &region_spec);
     const PartLayout L = lay_out(b, wspecs.size(), region_spec.size());
-    NMRFIT_HIP_OR(hipMalloc(&b->d_block, L.total), part_destroy(b));
+    NMRFIT_HIP_OR(device_alloc(&b->d_block, L.total), part_destroy(b));
     unsigned char *base = reinterpret_cast<unsigned char *>(b->d_block);
     NMRFIT_HIP_OR(hipMemsetAsync(base, 0, L.zeroed, b->stream), part_destroy(b));
     const std::vector<BatchFit> tabs = build_tables(b, L, base, w, params);

@@ -39,7 +39,7 @@ static int part_contributions_enqueue(BatchPart *b, const int64_t *Nout, const d
     const int64_t n_data = data_out ? 2 * b->noff[(size_t)K] : 0;
     if (2 * n_contrib + n_fit + n_data == 0) return NMRFIT_OK;
     const size_t jobs_bytes = align256((size_t)K * sizeof(ResultJob));
-    NMRFIT_HIP(hipMalloc(&b->d_result, jobs_bytes + (size_t)(n_w + 2 * n_contrib + n_fit + n_data) * sizeof(double)));
+    NMRFIT_HIP(device_alloc(&b->d_result, jobs_bytes + (size_t)(n_w + 2 * n_contrib + n_fit + n_data) * sizeof(double)));
     unsigned char *base = reinterpret_cast<unsigned char *>(b->d_result);
     double *d_w = reinterpret_cast<double *>(base + jobs_bytes);
     double *d_real = d_w + n_w, *d_imag = d_real + n_contrib, *d_fit = d_imag + n_contrib, *d_data = d_fit + n_fit;
@@ -174,7 +174,7 @@ static int part_quality_enqueue(BatchPart *b, const double *x, const int32_t *R,
         if (b->d_quality) (void)hipFree(b->d_quality);
         b->d_quality = nullptr;
         b->cap_quality = 0;
-        NMRFIT_HIP(hipMalloc(&b->d_quality, c.total));
+        NMRFIT_HIP(device_alloc(&b->d_quality, c.total));
         b->cap_quality = c.total;
     }
     unsigned char *base = reinterpret_cast<unsigned char *>(b->d_quality);

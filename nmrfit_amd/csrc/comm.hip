@@ -11,7 +11,7 @@
 // users never load it and the library has no link-time dependency on it.  No PyTorch anywhere:
 // the 128-byte unique id travels between the ranks however the caller likes (the Python side
 // uses stdlib sockets, nmrfit_amd/rendezvous.py).
-#include "nmrfit_internal.h"
+#include "host_call.h"
 #include "nmrfit_amd_diag.h"
 
 #include <dlfcn.h>
@@ -154,7 +154,7 @@ int comm_all_gather(nmrfit_comm *c, hipStream_t stream, const double *d_send, in
         if (c->d_gather) NMRFIT_HIP(hipFree(c->d_gather));
         c->d_gather = nullptr;
         c->gather_cap = 0;
-        NMRFIT_HIP(hipMalloc((void **)&c->d_gather, (size_t)(n * c->nranks) * sizeof(double)));
+        NMRFIT_HIP(device_alloc((void **)&c->d_gather, (size_t)(n * c->nranks) * sizeof(double)));
         c->gather_cap = n * c->nranks;
     }
     NMRFIT_RCCL(g_rccl.AllGather(d_send, c->d_gather, (size_t)n, ncclDouble, c->comm, stream));
@@ -221,11 +221,11 @@ int nmrfit_comm_create(nmrfit_ctx *ctx, int32_t rank, int32_t nranks, const void
         return rccl_fail(r, "ncclCommInitRank", __LINE__);
     }
     c->scratch_cap = kScratch * (1 + nranks);
-    hipError_t e = hipMalloc((void **)&c->d_scratch, (size_t)c->scratch_cap * sizeof(double));
+    hipError_t e = device_alloc((void **)&c->d_scratch, (size_t)c->scratch_cap * sizeof(double));
     if (e != hipSuccess) {
         (void)g_rccl.CommDestroy(c->comm);
         delete c;
-        return hip_fail(e, "hipMalloc(comm scratch)", __FILE__, __LINE__);
+        return hip_fail(e, "device_alloc(comm scratch)", __FILE__, __LINE__);
     }
     *out = c;
     return NMRFIT_OK;

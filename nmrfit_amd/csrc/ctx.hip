@@ -20,7 +20,7 @@ int ensure(nmrfit_ctx *ctx, double **buf, int64_t *cap, int64_t need)
     *buf = nullptr;
     *cap = 0;
     int64_t n = need + need / 4 + 64;
-    NMRFIT_HIP(hipMalloc((void **)buf, (size_t)n * sizeof(double)));
+    NMRFIT_HIP(device_alloc((void **)buf, (size_t)n * sizeof(double)));
     *cap = n;
     return NMRFIT_OK;
 }
@@ -115,7 +115,7 @@ int nmrfit_ctx_create(int device, int64_t N, const double *w, const double *u, c
     Carver c;
     const size_t o_wc = c.take(padded), o_u = c.take(padded), o_v = c.take(padded), o_wt = c.take(padded);
     const size_t o_chunk = c.take((size_t)ctx->n_chunks * sizeof(double2)), o_stage = c.take(bytes);
-    NMRFIT_HIP_OR(hipMalloc((void **)&ctx->d_block, c.total), nmrfit_ctx_destroy(ctx));
+    NMRFIT_HIP_OR(device_alloc((void **)&ctx->d_block, c.total), nmrfit_ctx_destroy(ctx));
     // (the four grid arrays: their padding is zeros, weight 0)
     NMRFIT_HIP_OR(hipMemsetAsync(ctx->d_block, 0, o_chunk, ctx->stream), nmrfit_ctx_destroy(ctx));
     unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_block);
@@ -237,7 +237,7 @@ int nmrfit_dev_alloc(nmrfit_ctx *ctx, int64_t bytes, void **dptr)
     }
     *dptr = nullptr;
     if (bytes == 0) return NMRFIT_OK;
-    NMRFIT_HIP(hipMalloc(dptr, (size_t)bytes));
+    NMRFIT_HIP(device_alloc(dptr, (size_t)bytes));
     return NMRFIT_OK;
 }
 
@@ -322,7 +322,7 @@ int nmrfit_prof_enable(nmrfit_ctx *ctx, int64_t capacity)
 #else
         constexpr size_t kClkWords = 4;
 #endif
-        NMRFIT_HIP(hipMalloc((void **)&ctx->d_clk, kClkWords * sizeof(unsigned long long)));
+        NMRFIT_HIP(device_alloc((void **)&ctx->d_clk, kClkWords * sizeof(unsigned long long)));
         NMRFIT_HIP(hipMemsetAsync(ctx->d_clk, 0, kClkWords * sizeof(unsigned long long), ctx->stream));
     }
     for (int64_t i = 0; i < capacity; ++i) {

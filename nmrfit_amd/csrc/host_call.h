@@ -7,7 +7,14 @@
 #include <algorithm>
 #include <vector>
 
+#include "poison_knob.h"
+
 namespace nmrfit {
+
+// The one home of device allocation: every hipMalloc of the library is this call (host_call.hip).  With the diagnostic
+// NMRFIT_POISON_ALLOC=<byte> (poison_knob.h) the new block is filled with that byte, and the fill is
+// complete on return -- so that no result can lean on what a fresh block happens to hold (the audit table).
+hipError_t device_alloc(void **p, size_t bytes);
 
 // A HIP call while an object is half built: on failure the error is recorded with the call's own file and line,
 // `cleanup` (the object's destroy call) runs, and the enclosing function returns the code.
@@ -84,7 +91,7 @@ struct Scratch {
     hipError_t alloc(T **p, size_t n)
     {
         void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
+        hipError_t e = device_alloc(&q, std::max<size_t>(n, 1) * sizeof(T));
         if (e == hipSuccess) ptrs.push_back(q);
         *p = (T *)q;
         return e;

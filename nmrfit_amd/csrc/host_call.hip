@@ -24,6 +24,21 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
     return NMRFIT_E_HIP;
 }
 
+// (the knob is read once per process; unset: one predictable branch.  The fill is the runtime's memset on the null stream and
+// a wait of its own: the library's streams are non-blocking, so nothing else orders it before the caller's first use)
+hipError_t device_alloc(void **p, size_t bytes)
+{
+    static const int poison = parse_poison_byte(getenv("NMRFIT_POISON_ALLOC"));
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess || poison < 0) return e;
+    if ((e = hipMemset(*p, poison, bytes)) == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    return e;
+}
+
 // A context's own stream, recycled: a new HIP stream costs about 4 ms on this stack when it is first used (the hardware
 // queue behind it is made then; measured, tools/archive/hip_call_costs.hip) and a whole default fit is 25 ms -- a fit
 // that pyswarm's rule stops after a few hundred generations 3 ms.  Contexts that come and go (one per fitted spectrum)

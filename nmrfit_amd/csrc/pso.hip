@@ -662,7 +662,7 @@ int nmrfit_pso_create(nmrfit_ctx *ctx, int64_t S_local, int64_t S_global, int64_
     if (getenv("NMRFIT_NO_FUSED_TAIL")) pso->fused_tail = false;     // A/B knob
     const size_t sd = (size_t)std::max<int64_t>(S_local * D, 1) * sizeof(double);
     const size_t s1 = (size_t)std::max<int64_t>(S_local, 1) * sizeof(double);
-    // ONE allocation for the whole swarm state (every hipMalloc / hipFree is a synchronising call; a default fit
+    // ONE allocation for the whole swarm state (every allocation and hipFree is a synchronising call; a default fit
     // is 30 ms).  Layout: 256-byte aligned pieces; fp[S] right behind p[S x D] (the objective kernel's fused
     // personal-best step finds fp from p without another pointer argument, objective.hip).
     {
@@ -676,7 +676,7 @@ int nmrfit_pso_create(nmrfit_ctx *ctx, int64_t S_local, int64_t S_global, int64_
         const size_t o_best = c.take(2 * state_bytes), o_p_alt = c.take(p_bytes);
         const size_t o_part_val = c.take(nposts * sizeof(double)), o_part_idx = c.take(nposts * sizeof(long long));
         const size_t o_ticket = c.take(256);
-        NMRFIT_HIP_OR(hipMalloc(&pso->d_block, c.total), nmrfit_pso_destroy(pso));
+        NMRFIT_HIP_OR(device_alloc(&pso->d_block, c.total), nmrfit_pso_destroy(pso));
         unsigned char *base = reinterpret_cast<unsigned char *>(pso->d_block);
         pso->d_lb = reinterpret_cast<double *>(base + o_lb);
         pso->d_ub = reinterpret_cast<double *>(base + o_ub);
@@ -766,6 +766,8 @@ int nmrfit_pso_candidate_dev(nmrfit_pso *pso, double **dptr)
     }
     int rc = bind_pso(pso);
     if (rc != NMRFIT_OK) return rc;
+    // (the record is written by generation 0: before it the buffer holds whatever the allocation did)
+    if (!pso->initialized) return refuse(NMRFIT_E_STATE, "nmrfit_pso_candidate_dev before nmrfit_pso_init");
     if ((rc = flush_fold(pso)) != NMRFIT_OK) return rc;   // (the record of the LAST generation, on the stream before any copy)
     *dptr = pso->d_cand;
     return NMRFIT_OK;
@@ -977,6 +979,9 @@ int nmrfit_pso_get_state(nmrfit_pso *pso, double *x, double *v, double *p, doubl
 {
     int rc = bind_pso(pso);
     if (rc != NMRFIT_OK) return rc;
+    // (x, v, p, fx, fp are written by generation 0: before it they hold whatever the allocation did.  nmrfit_pso_status and
+    // nmrfit_pso_best are defined from creation on: the state blocks are zeroed there)
+    if (!pso->initialized) return refuse(NMRFIT_E_STATE, "nmrfit_pso_get_state before nmrfit_pso_init");
     if ((rc = flush_fold(pso)) != NMRFIT_OK) return rc;
     hipStream_t st = pso->ctx->stream;
     const size_t sd = (size_t)(pso->S * pso->D) * sizeof(double), s1 = (size_t)pso->S * sizeof(double);
