@@ -18,6 +18,10 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.noise.replicas(us, vs, sigma_u, sigma_v, seeds)   the noisy copies alone (noise.normals / replicas_host: the numpy mirror)
     nmrfit_amd.fit_many(jobs, quality=True)                      every fit carries fit.quality: residual statistics per peak region,
                                                                  reduced on the DEVICE (residual_stats / residual_stats_many alone)
+    nmrfit_amd.sample_noise_many(ws, ys, regions)                utils.sample_noise for many spectra on the DEVICE (baseline.fit_many:
+                                                                 a conditioned polynomial fit over a masked part of a grid)
+    nmrfit_amd.correct_baseline_many(datas, deg=1)               a polynomial baseline fitted outside the peaks and taken out of V, I, u, v
+    nmrfit_amd.fit_many(jobs, residual_baseline=1)               every fit carries fit.residual_baseline: the baseline of data_V - V
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
@@ -29,9 +33,10 @@ bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
-from . import batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, utils  # noqa: F401
+from . import baseline, batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, utils  # noqa: F401
 from .quality import FitQuality, residual_stats, residual_stats_many  # noqa: F401
 from .noise import fit_replicas, fit_replicas_many  # noqa: F401
-from .containers import Data, select_peaks_many, shift_phase_many  # noqa: F401
+from .containers import Data, correct_baseline_many, select_peaks_many, shift_phase_many  # noqa: F401
+from .baseline import BaselineFit, sample_noise_many, subtract_rotated  # noqa: F401
 
 __version__ = "0.1.0"

@@ -182,7 +182,13 @@ QUALITY_SIGNATURES = {
     "nmrfit_quality_stats": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_batch_quality_stats": [_VP, _VP, _VP, _VP, _VP],
 }
-LSQ_MAX_D = 76                    # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
+# BASELINE_SIGNATURES: include/nmrfit_amd_baseline.h (least-squares polynomial baselines and noise levels over a masked
+# part of a grid, from host arrays or on the residual of a batch's resident fits)
+BASELINE_SIGNATURES = {
+    "nmrfit_baseline_fit": [_INT, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_residual_baseline": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
+LSQ_MAX_D = 76                   # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
 _LIB = None
@@ -285,7 +291,8 @@ def lib():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
-                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()):
+                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
+                + list(BASELINE_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -235,6 +235,36 @@ class FitBatch:
                                                          _cabi.ptr(edges) if edges.size else None, _cabi.ptr(out)))
         return quality.split_rows(out, R, self.D)
 
+    # -- residual baseline (include/nmrfit_amd_baseline.h) ------------------------------------------
+    def residual_baseline(self, X=None, deg=1, intervals=None, complement=True, return_baseline=False):
+        """Per fit a ``baseline.BaselineFit``: a least-squares polynomial of degree ``deg`` fitted to the residual
+        ``data_V - V`` of every fit over a masked part of its grid, on the batch's resident spectra (csrc/baseline.hip) --
+        17 doubles per fit come back instead of the arrays of ``generate``.  ``X``: the K parameter vectors, allowed in any
+        state; None: every fit's best position (``NmrfitError`` with the state code before the first generation).
+        ``intervals``: None, or K lists of ``(lo, hi)`` in units of w; ``complement=True`` (the default) fits OUTSIDE them
+        -- give the peaks' regions; with no intervals that is the whole grid.  ``deg``, ``complement``: one value or one
+        per fit.  ``return_baseline``: also the polynomial at every grid point (``BaselineFit.baseline``).  Bit for bit
+        ``baseline.fit_many`` on the ``data_V - V`` of ``generate()``.  The swarms are not touched."""
+        from . import baseline
+        d, R, edges, comp = baseline.pack_jobs(self.K, deg, intervals, complement)
+        x = None
+        if X is not None:
+            if len(X) != self.K:
+                raise ValueError("FitBatch.residual_baseline: one parameter vector per fit")
+            X = [_cabi.f64(xk).ravel() for xk in X]
+            for k, xk in enumerate(X):
+                if xk.shape != (self.D[k],):
+                    raise ValueError("FitBatch.residual_baseline: fit %d takes %d parameters" % (k, self.D[k]))
+            x = np.concatenate(X)
+        rows = np.empty(self.K * baseline.ROW)
+        base = np.empty(int(self.noff[-1])) if return_baseline else None
+        _cabi.check(self._lib.nmrfit_batch_residual_baseline(self._h, _cabi.ptr(x), _cabi.ptr(d), _cabi.ptr(R),
+                                                             _cabi.ptr(edges) if edges.size else None, _cabi.ptr(comp),
+                                                             _cabi.ptr(rows), _cabi.ptr(base)))
+        rows = rows.reshape(self.K, baseline.ROW)
+        return [baseline.BaselineFit(rows[k], base[self.noff[k]:self.noff[k + 1]].copy() if return_baseline else None)
+                for k in range(self.K)]
+
     # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
     def normal_equations(self, X, channels="real"):
         """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``

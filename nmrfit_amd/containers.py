@@ -162,3 +162,44 @@ def select_peaks_many(datas, method='auto', thresh=0.0, window=0.02, device=0):
         d.peaks = p
         d.roibounds = [q.bounds for q in p]
     return datas
+
+
+def correct_baseline_many(datas, deg=1, exclude=None, margin=1.0, device=0):
+    """Fit a polynomial baseline of degree ``deg`` to the channels V and I of every Data, outside its peaks, on the GPU
+    (baseline.fit_many, csrc/baseline.hip: a conditioned basis, a fixed summation order) and take it out: sets NEW
+    arrays ``V``, ``I``, ``u, v = ps2(V, I, p0, p1, inv=True)`` and ``d.baseline`` (the pair of ``BaselineFit``, with the
+    subtracted arrays in ``.baseline``).  The arrays the caller holds are never written in place.
+
+    exclude : per Data a list of ``(lo, hi)`` in units of w that the fit leaves out; default: the bounds of its peaks,
+        widened about their centres by ``margin``
+    margin : the peaks' bounds are a few widths wide: +-2 FWHM still leaves 1/17 of a Lorentzian's height just outside
+        them, and that tail is fitted as baseline.  A larger ``margin`` moves the fitted points further out (3: +-6 FWHM,
+        under 1/145 of the height), at the price of fewer of them.
+
+    ValueError if len(w) != len(V) (a Data cropped and not re-phased, as select_peaks_many), and -- before anything is
+    written to any Data: all or nothing -- if any job could not be fitted (an empty mask, fewer points than
+    coefficients), naming the spectrum."""
+    from . import baseline
+    datas = list(datas)
+    for k, d in enumerate(datas):
+        if not len(d.w) == len(d.V) == len(d.I):
+            raise ValueError("correct_baseline_many: len(w) != len(V) (spectrum %d): call shift_phase after select_bounds" % k)
+    if exclude is None:
+        exclude = [baseline.widened([tuple(p.bounds) for p in getattr(d, "peaks", [])], margin) for d in datas]
+    if len(exclude) != len(datas):
+        raise ValueError("correct_baseline_many: one list of excluded intervals per spectrum")
+    got = baseline.fit_many([d.w for d in datas], [np.array([d.V, d.I], dtype=np.float64) for d in datas], deg=deg,
+                            intervals=list(exclude), complement=True, device=device, return_baseline=True)
+    for k, pair in enumerate(got):
+        for name, b in zip("VI", pair):
+            if b.status != 0:
+                raise ValueError("correct_baseline_many: channel %s of spectrum %d could not be fitted (status %d: %s; "
+                                 "%d points outside the excluded intervals, degree %d)"
+                                 % (name, k, b.status, "empty mask" if b.status == 1 else "rank", b.n, b.deg))
+    for d, (bV, bI) in zip(datas, got):
+        V = np.asarray(d.V, dtype=np.float64) - bV.baseline
+        I = np.asarray(d.I, dtype=np.float64) - bI.baseline
+        d.V, d.I = V, I
+        d.u, d.v = proc_autophase.ps2(V, I, getattr(d, "p0", 0.0), getattr(d, "p1", 0.0), inv=True)
+        d.baseline = (bV, bI)
+    return datas

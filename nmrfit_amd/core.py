@@ -36,7 +36,7 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
 
 
 def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
-             batch_polish=False, quality=False, **kwargs):
+             batch_polish=False, quality=False, residual_baseline=None, **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -105,11 +105,23 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       ``FitBatch.residual_stats`` while the batch is resident (those with ``options['polish']`` are refined before
       that, not after the batch has closed), the fits that ran alone through one ``residual_stats_many`` call per
       device.  ``params`` and ``error`` do not change.  With ``shard=True`` the rows stay on the rank that made them,
-      like the arrays of ``generate``."""
+      like the arrays of ``generate``.
+    * ``residual_baseline=deg`` (or a dict: ``deg``, ``margin``, ``intervals``, ``complement``, ``return_baseline``): every
+      returned fit carries ``fit.residual_baseline`` (``nmrfit_amd.baseline.BaselineFit``): a least-squares polynomial of
+      that degree fitted to the residual ``data_V - V`` at its FINAL ``params`` outside its peaks' bounds (widened about
+      their centres by ``margin``; or over the caller's ``intervals``) -- where the Lorentzian tails of the main line are
+      already accounted for -- in a conditioned basis and a fixed summation order (include/nmrfit_amd_baseline.h), 17
+      doubles per fit.  The fits of a device batch go through ``FitBatch.residual_baseline`` while the batch is resident
+      (those with ``options['polish']`` are refined before that), the fits that ran alone through ``generate_result``'s
+      arrays and one ``baseline.fit_many`` call per device: the same V and data_V bits, the same rows.  ``params`` and
+      ``error`` do not change and nothing is refitted: ``baseline.subtract_rotated`` and a second ``fit_many`` are the
+      recipe.  With ``shard=True`` the rows stay on the rank that made them."""
+    from . import baseline as _baseline
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights),
-                 "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish), bool(quality))
+                 "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish), bool(quality),
+                 _baseline.option(residual_baseline))
     if devices is not None:
         if shard:
             raise ValueError("fit_many: shard=True divides the jobs over PROCESSES, devices=[...] over the GPUs of this "
@@ -139,6 +151,7 @@ class _Call(typing.NamedTuple):
     device_weights: bool
     batch_polish: object         # False, True (fit_im=False jobs), or "both" (the jobs of fit_im batches too, on both channels)
     quality: bool = False        # every fit gets ``quality``: its residual statistics per peak region (quality.py)
+    residual_baseline: object = None   # None, or baseline.option()'s dict: every fit gets ``residual_baseline`` (baseline.py)
 
 
 def _result_record(f):
@@ -268,6 +281,7 @@ class _Batch:
     def __init__(self, fb, fits, plans, key, idx):
         self.fb, self.fits, self.plans, self.key, self.idx = fb, fits, plans, key, idx
         self.quality = None      # read(), ``call.quality``: the fits' FitQuality, made while the batch was resident
+        self.residual_baseline = None      # read(), ``call.residual_baseline``: the fits' BaselineFit, likewise
 
     @classmethod
     def create(cls, fits, plans, key, idx):
@@ -299,7 +313,8 @@ class _Batch:
         (FitBatch.polish); their entries of ``best`` are then the refined ones and their indices come back as
         ``refined``: store leaves them alone.  ``call.quality``: the residual statistics of every fit at its final
         parameters, from the resident spectra (FitBatch.residual_stats) -- the fits store would refine one by one are
-        refined here first and count as ``refined``.  Closes the batch.  Returns (refined, status, best, results)."""
+        refined here first and count as ``refined``.  ``call.residual_baseline``: the same for the polynomial baseline of
+        every fit's residual (FitBatch.residual_baseline).  Closes the batch.  Returns (refined, status, best, results)."""
         fits, fb, refined = self.fits, self.fb, set()
         polished = sum(1 for f in fits if f.options.get('polish', False))
         try:
@@ -320,6 +335,9 @@ class _Batch:
             if call.quality:
                 refined |= self._refine_per_fit(call, refined, best)
                 self.quality = fb.residual_stats([x for x, _ in best], [_peak_regions(f) for f in fits])
+            if call.residual_baseline is not None:
+                refined |= self._refine_per_fit(call, refined, best)
+                self.residual_baseline = _residual_baseline_resident(fb, call.residual_baseline, fits, [x for x, _ in best])
         finally:
             fb.close()
         return refined, status, best, results
@@ -358,6 +376,8 @@ class _Batch:
             f._finish(x, fx)
             if self.quality is not None:
                 f.quality = self.quality[k]
+            if self.residual_baseline is not None:
+                f.residual_baseline = self.residual_baseline[k]
             if k in polished:
                 if scale is not False:
                     f.generate_result(scale)      # (from the refined parameters: the batch's launch used the swarm's)
@@ -489,6 +509,26 @@ def _peak_regions(f):
     return [tuple(p.bounds) for p in f.data.peaks]
 
 
+def _residual_baseline_resident(fb, opts, fits, X):
+    """``FitBatch.residual_baseline`` at ``X`` under the call's options (baseline.option)."""
+    from . import baseline
+    picked = [baseline.fit_intervals(opts, f) for f in fits]
+    return fb.residual_baseline(X, deg=opts["deg"], intervals=[iv for iv, _ in picked], complement=[c for _, c in picked],
+                                return_baseline=opts["return_baseline"])
+
+
+def _residual_baseline_alone(fits, idx, opts, device):
+    """The same for fits that ran alone: the residual from ``generate_result``'s arrays (scale 1: the reconstruction's V
+    and data_V bits), one ``baseline.fit_many`` call."""
+    from . import baseline
+    ys = [fits[i].residual_arrays() for i in idx]
+    picked = [baseline.fit_intervals(opts, fits[i]) for i in idx]
+    got = baseline.fit_many([fits[i].data.w for i in idx], ys, deg=opts["deg"], intervals=[iv for iv, _ in picked],
+                            complement=[c for _, c in picked], device=device, return_baseline=opts["return_baseline"])
+    for i, b in zip(idx, got):
+        fits[i].residual_baseline = b
+
+
 def _fit_alone(fits, plans, alone, call):
     """The fits that ran in no batch, through fit() -- with the plan made for them, if any -- on ``call.threads``
     threads; serially when any carries an ``exchange`` (a communicator serves one swarm at a time).  ``call.quality``:
@@ -513,4 +553,10 @@ def _fit_alone(fits, plans, alone, call):
                                               [fits[i].params for i in idx], [_peak_regions(fits[i]) for i in idx], device=device)
             for i, q in zip(idx, got):
                 fits[i].quality = q
+    if call.residual_baseline is not None:
+        by_device = {}
+        for i in alone:
+            by_device.setdefault(fits[i]._device(), []).append(i)
+        for device, idx in by_device.items():
+            _residual_baseline_alone(fits, idx, call.residual_baseline, device)
     return fits

@@ -159,13 +159,41 @@ def _job_sigma(job, data):
     return pair
 
 
-def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, **kwargs):
+def _device_sigmas(jobs, shared, device):
+    """``_job_sigma`` of every job that gives a ``noise_region`` (its own, or the shared one) and no ``sigma``, from ONE
+    ``baseline.sample_noise_many`` call on both channels; {job index: (sigma_u, sigma_v)}."""
+    from .baseline import sample_noise_many
+    idx, regions = [], []
+    for m, job in enumerate(jobs):
+        src = job if job.get("sigma") is not None or job.get("noise_region") is not None else shared
+        if src.get("sigma") is None and src.get("noise_region") is not None:
+            idx.append(m)
+            regions.append(tuple(src["noise_region"]))
+    if not idx:
+        return {}
+    datas = [dict(shared, **jobs[m])["data"] for m in idx]
+    got = sample_noise_many([d.w for d in datas], [np.array([d.u, d.v], dtype=np.float64) for d in datas], regions, device=device)
+    out = {}
+    for m, pair in zip(idx, got):
+        pair = (float(pair[0]), float(pair[1]))
+        if not all(np.isfinite(s) and s >= 0.0 for s in pair):
+            raise ValueError("fit_replicas: sigma must be finite and >= 0, got %r" % (pair,))
+        out[m] = pair
+    return out
+
+
+def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, device_sigma=False, **kwargs):
     """``fit_replicas`` for several spectra at once: ``jobs`` as ``fit_many`` takes them -- ``(data, lower, upper)``
     triples or dicts of ``fit``'s arguments -- each with its own ``sigma`` or ``noise_region`` (or the shared keyword).
     All M x K fits are packed into ragged device batches of at most ``core.BATCH_JOBS_MAX`` fits.  Fit k of job m
     (k = 0: the original data, k = 1 .. replicas: the noisy copies) has swarm seed and noise seed
     ``seed + m * (replicas + 1) + k``, whether the original is included or not -- ``options['seed']`` is not used: the
     seeds of a replica study come from the ``seed`` keyword alone.  Returns one ``ReplicaFits`` per job.
+
+    ``device_sigma=True``: the sigmas of all jobs that give a ``noise_region`` come from one
+    ``baseline.sample_noise_many`` call (csrc/baseline.hip: the same quadratic fit in a conditioned basis, on the device
+    ``options['device']`` names) instead of two ``sample_noise`` calls per job on the host; they agree with the host's to
+    the conditioning of ``np.polyfit`` on raw ppm values, not bit for bit, so the default stays the host path.
 
     Every fit runs in a device batch: ``options['exchange']``, ``options['polish']`` and kernel variants a batch does
     not run are refused (ValueError)."""
@@ -178,12 +206,13 @@ def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, **kwargs
     kwargs.pop("processes", None)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     ks = list(range(0 if include_original else 1, replicas + 1))
+    sigmas = _device_sigmas(jobs, kwargs, int((kwargs.get("options") or {}).get("device") or 0)) if device_sigma else {}
     entries, per_job = [], []          # every fit of the call: (job, its place in the job's list); per job: plan, fits, ...
     for m, job in enumerate(jobs):
         args = dict(kwargs, **job)
         data = args["data"]
         own = job.get("sigma") is not None or job.get("noise_region") is not None      # (a job's own beats the shared one)
-        sigma = _job_sigma(job if own else kwargs, data)
+        sigma = sigmas[m] if m in sigmas else _job_sigma(job if own else kwargs, data)
         fa = {k: v for k, v in args.items() if k not in ("data", "lower", "upper", "sigma", "noise_region")}
         base = utils.FitUtility(data, args["lower"], args["upper"], **fa)
         if base.options.get("exchange") is not None or base.options.get("polish", False):

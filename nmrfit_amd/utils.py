@@ -472,6 +472,16 @@ class FitUtility:
                                               device=self._device())
         return self.quality
 
+    def residual_arrays(self):
+        """``data_V - V`` of this finished fit on its own grid, from the arrays of ``generate_result`` (one launch of the
+        reconstruction kernel: the bits a device batch's ``residual_baseline`` works on); nothing is stored."""
+        ev = equations.Evaluator(self.data.w, self.data.u, self.data.v, np.ones(len(self.data.w)), device=self._device())
+        try:
+            _, _, fit, rotated = ev.generate_result(self.params, None)
+        finally:
+            ev.close()
+        return rotated[0] - fit[0]
+
     def get_areas(self):
         """utils.py:312-322."""
         return np.array([self.params[i] for i in range(6, len(self.params), 3)])

@@ -5,7 +5,8 @@ remarks (no GPU needed): compiles each .hip of nmrfit_amd/csrc for gfx950 with
 non-zero `scratch` column; `tools/kernel_resources.py --check` exits 1 if any objective_kernel
 instantiation that nmrfit_amd.fit() can select (variants DEFAULT / FARFIELD / NOREC, with or without
 the imaginary channel, plus every residual form) uses scratch memory, or if the pair form of the DEFAULT objective
-kernel (objective_pair.hip) leaves its budget: at most 128 VGPRs, no scratch, four waves per SIMD.
+kernel (objective_pair.hip) leaves its budget: at most 128 VGPRs, no scratch, four waves per SIMD, or if a kernel of
+baseline.hip (every degree class of the job kernel, the residual gather) uses scratch memory or spills.
 
     python tools/kernel_resources.py [--check] [--unit objective_pair.hip ...] [extra hipcc flags, e.g. -DNMRFIT_POINTS=4]
 """
@@ -28,7 +29,7 @@ def demangle(names):
 def resources(extra, units=()):
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in units or ("objective_default.hip", "objective_pair.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip"):
+        for src in units or ("objective_default.hip", "objective_pair.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip", "baseline.hip"):
             if not os.path.exists(os.path.join(CSRC, src)):
                 continue
             cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
@@ -93,8 +94,11 @@ def main():
         # the pair form pays only while it runs four waves per SIMD
         if pair and (scratch or int(r.get("VGPRs", "999")) > 128 or int(r.get("Occupancy [waves/SIMD]", "0")) < 4):
             bad.append(label)
+        # the polynomial baselines carry up to 26 running sums per lane: every degree class stays in registers
+        if name.startswith("baseline_") and (scratch or int(r.get("VGPRs Spill", "0")) or int(r.get("SGPRs Spill", "0"))):
+            bad.append(label)
     if check and bad:
-        print("SPILLS in kernels fit() can select (or the pair form outside 128 VGPRs / four waves):", bad)
+        print("SPILLS in kernels fit() can select or in baseline.hip (or the pair form outside 128 VGPRs / four waves):", bad)
         return 1
     return 0
 
