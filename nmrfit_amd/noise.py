@@ -7,7 +7,9 @@ normal deviates) -- and leaves the loop to the user, K fits of minutes each.  He
 ``fit_replicas`` tiles the spectrum into ``FitBatch``es, the copies are made on the device in place
 (``FitBatch.add_noise``; csrc/noise.hip, include/nmrfit_amd_noise.h) and every replica runs exactly as ``fit`` would run
 it on that copy.  No Jacobian, no linearisation at a box-constrained optimum, and the swarm's own scatter -- a real part
-of the error of a particle-swarm fit -- is in the spread.
+of the error of a particle-swarm fit -- is in the spread; with ``options['polish']`` the replicas are refined on the
+resident batch (``FitBatch.polish``) and the spread is that of the least-squares minimisers, which
+tests/test_gpu_calibration.py holds replica by replica to the linear response of each replica's own noise.
 
 The deviates are a pure function of (noise seed, grid point): one Philox4x32-10 block per point (``pso.philox4x32_10``,
 counter ``(j lo, j hi, 0x4E4F4953, 0)``, key the seed) and one Box-Muller pair for the two channels.  ``normals`` is the
@@ -195,8 +197,22 @@ def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, device_s
     ``options['device']`` names) instead of two ``sample_noise`` calls per job on the host; they agree with the host's to
     the conditioning of ``np.polyfit`` on raw ppm values, not bit for bit, so the default stays the host path.
 
-    Every fit runs in a device batch: ``options['exchange']``, ``options['polish']`` and kernel variants a batch does
-    not run are refused (ValueError)."""
+    ``options['polish']``: every fit that has it is refined by ``FitBatch.polish`` while its batch is resident -- in lock
+    step, on the fit's own (noisy) spectrum, ``channels="both"`` in the batches of ``fit_im`` jobs -- and ``params`` /
+    ``error`` are the refined ones (never worse than the swarm's).  WITHOUT it every replica is a swarm result stopped by
+    pyswarm's rule, and the spread includes the optimiser's stopping error, which does not depend on the noise and adds
+    in quadrature.  Measured on exactly fitted two- and three-peak spectra at sigma = 1e-3 max|u| (DESIGN.md section 4.11,
+    profiles/r18/replica_calibration.txt): the default swarm of 204 stops a median 0.06 .. 0.4, at the 95th percentile
+    0.3 .. 4 and at worst 20 .. 76 standard errors from the replica's minimiser, and ``params_std`` comes out 1.0 .. 8.2
+    times (``area_fraction_std`` 1.0 .. 1.9 times) the noise-driven spread; with 64 particles 5 .. 70 times (5 .. 220).
+    With polish every replica is within 0.05 standard errors of the linear response to its own noise and the spreads are
+    the predicted ones to 0.3 %: ask for it when the spread is to be read as the noise's.  Fit 0 is then the lone
+    ``fit``'s swarm result refined by the batch's Levenberg-Marquardt loop, where a lone ``fit`` with the option runs
+    scipy's TRF: the same minimum to the stopping tolerances, not the same bits.  Fits beyond the least-squares kernel's
+    parameter count (``_cabi.LSQ_MAX_D``) in a batch that refines any: ValueError.
+
+    Every fit runs in a device batch: ``options['exchange']`` and kernel variants a batch does not run are refused
+    (ValueError)."""
     from . import core, utils
     from .batch import FitBatch
     replicas = int(replicas)
@@ -215,9 +231,8 @@ def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, device_s
         sigma = sigmas[m] if m in sigmas else _job_sigma(job if own else kwargs, data)
         fa = {k: v for k, v in args.items() if k not in ("data", "lower", "upper", "sigma", "noise_region")}
         base = utils.FitUtility(data, args["lower"], args["upper"], **fa)
-        if base.options.get("exchange") is not None or base.options.get("polish", False):
-            raise ValueError("fit_replicas: the replicas run as device batches: options['exchange'] and "
-                             "options['polish'] are not supported")
+        if base.options.get("exchange") is not None:
+            raise ValueError("fit_replicas: the replicas run as device batches: options['exchange'] is not supported")
         plan = base._plan()            # ONE plan per job: weights, swarm constants, variant, maxiter -- as fit makes it
         key = base._batch_key(plan)
         if key is None:
@@ -235,6 +250,12 @@ def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, device_s
     for e in entries:
         groups.setdefault(per_job[e[0]]["key"], []).append(e)
     for key, members in groups.items():
+        # (the rows launch of FitBatch.polish covers the whole batch: every fit of a batch that refines any)
+        fits = [per_job[m]["fits"][i] for m, i in members]
+        if any(f.options.get("polish", False) for f in fits) and max(len(f.lower) for f in fits) > _cabi.LSQ_MAX_D:
+            raise ValueError("fit_replicas: options['polish'] refines device batches of fits with at most %d parameters"
+                             % _cabi.LSQ_MAX_D)
+    for key, members in groups.items():
         for a in range(0, len(members), core.BATCH_JOBS_MAX):
             chunk = members[a:a + core.BATCH_JOBS_MAX]
             recs = [per_job[m] for m, _ in chunk]
@@ -250,6 +271,11 @@ def fit_replicas_many(jobs, replicas=32, seed=0, include_original=True, device_s
                     fb.add_noise(sig[:, 0], sig[:, 1], seeds)
                 fb.run(key.maxiter, key.check_every)
                 status, best = fb.status(), fb.best()
+                which = [j for j, f in enumerate(fits) if f.options.get("polish", False)]
+                if which:
+                    new = fb.polish([x for x, _ in best], which=which, **(dict(channels="both") if key.fit_im else {}))
+                    for j in which:
+                        best[j] = new[j]
             for (m, i), f, st, (x, fx) in zip(chunk, fits, status, best):
                 f._finish(x, fx)
                 per_job[m]["iterations"][i], per_job[m]["stop"][i] = st["iteration"], st["stop"]
@@ -271,6 +297,8 @@ def fit_replicas(data, lower, upper, replicas=32, sigma=None, noise_region=None,
         (``options['seed']`` is not used)
     include_original : fit 0 is the data as it is (sigma 0) -- bit for bit
         ``nmrfit_amd.fit(data, ..., options={..., 'seed': seed})`` -- and stays out of the statistics
+    options['polish'] : every replica is refined by least squares on the resident batch (``fit_replicas_many``); without
+        it the spread includes the swarm's stopping error, which on its own can be several times the noise's
 
     ``data`` itself is never written."""
     return fit_replicas_many([dict(data=data, lower=lower, upper=upper)], replicas=replicas, seed=seed,

@@ -9,6 +9,7 @@ import pytest
 import nmrfit_amd
 from nmrfit_amd import _cabi, noise, synth
 from nmrfit_amd.batch import FitBatch
+from tests import calibration_support as C
 from tests import noise_support as T
 
 pytestmark = pytest.mark.gpu
@@ -115,7 +116,8 @@ def test_in_place(seven):
 @pytest.mark.parametrize("fit_im", [False, True])
 def test_chain(seven, fit_im):
     """The fits that follow: a batch uploaded with the host copies of the replicas and a batch perturbed in place give
-    the same best() after 30 generations; with every sigma 0 the call changes nothing."""
+    the same best() after 30 generations; with every sigma 0 the call changes nothing.  Real channel: two replicas of
+    ONE spectrum under different noise seeds move as their own noise predicts, each its own way (``check_two_seeds``)."""
     specs, noisy = seven
     with make_batch(specs, uv=noisy, fit_im=fit_im) as fa, make_batch(specs, fit_im=fit_im) as fb:
         fb.add_noise(SIGMA_U, SIGMA_V, SEEDS)
@@ -130,6 +132,30 @@ def test_chain(seven, fit_im):
         c, d = fc.best(), fd.best()
     assert same_best(c, d)
     assert not same_best(a, c)                                            # (the noise does reach the fits)
+    if not fit_im:
+        check_two_seeds()
+
+
+def check_two_seeds():
+    """Replicas 1 and 2 of tests/calibration_support.py's first case (an exactly fitted spectrum, noise seeds 101 and
+    102), run and polished beside the unperturbed fit: D_k = x_k - x0 is within the bar of the linear response to its own
+    noise, so the two are as uncorrelated as their predictions -- sum_i D_1i D_2i / sigma_x,i^2 equals the predictions'
+    within b (|L_1| + |L_2|) + b^2 per parameter -- and not one draw used twice."""
+    c, t = C.case("n512_p2"), C.truth("n512_p2")
+    b = C.bar(c)
+    with FitBatch([c.spectrum_tuple()] * 3, [c.lower] * 3, [c.upper] * 3, swarmsize=64, seeds=c.seeds[:3]) as fb:
+        fb.add_noise([0.0, c.sigma_u, c.sigma_u], [0.0, c.sigma_v, c.sigma_v], c.seeds[:3])
+        fb.run()
+        got = fb.polish(max_launches=200, ftol=C.FTOL)
+        assert all(st in ("ftol", "lambda") for st in fb.last_polish["stop"])      # (converged: not the budget)
+    d = (np.array([x for x, _ in got])[1:] - t.x0) / t.sigma_x
+    lin = t.lin[:2] / t.sigma_x
+    assert np.all(np.abs(d - lin) <= b)
+    tol = np.sum(b * (np.abs(lin[0]) + np.abs(lin[1])) + b * b)
+    print("two seeds: sum D_1 D_2 / sigma_x^2 = %.4f, predicted %.4f, tolerance %.4f; against one draw twice: %.4f"
+          % (d[0] @ d[1], lin[0] @ lin[1], tol, lin[0] @ lin[0]))
+    assert abs(d[0] @ d[1] - lin[0] @ lin[1]) <= tol
+    assert abs(lin[0] @ lin[0] - lin[0] @ lin[1]) > tol                   # (the check tells the two apart)
 
 
 def test_state(seven):
@@ -161,8 +187,12 @@ def test_state(seven):
 
 
 def test_end_to_end():
-    """fit_replicas: fit 0 is the lone fit bit for bit, the call repeats, the spread is a number, the data is not
-    written; fit_replicas_many gives job 0 the same params."""
+    """fit_replicas: fit 0 is the lone fit bit for bit, the call repeats, the data is not written; fit_replicas_many
+    gives job 0 the same params.  The spread: with ``options['polish']`` every noisy fit is within the bar of the Newton
+    prediction of its own noise (tests/calibration_support.py, case "end_to_end": this spectrum, these seeds; the base is
+    noisy, so the prediction takes the full Hessian) and ``params_std`` / ``area_fraction_std`` are the predictions'
+    spreads within the bar's propagation; the swarm alone (this test's 64 particles, 300 generations) never has the
+    smaller error and its spread is printed beside them."""
     opts = {'swarmsize': 64, 'maxiter': 300}
     spec = synth.make_spectrum(1024, 2, noise=1e-3, physical=True)
     data = synth.SynthData(spec["w"], spec["u"], spec["v"], spec["peaks"])
@@ -174,6 +204,23 @@ def test_end_to_end():
     assert rf.seeds == list(range(11, 20)) and np.array_equal(rf.sigma[0], [0.0, 0.0]) and np.all(rf.sigma[1:] == spec["sigma"])
     again = nmrfit_amd.fit_replicas(data, spec["lower"], spec["upper"], replicas=8, sigma=spec["sigma"], seed=11, options=opts)
     assert np.array_equal(again.params, rf.params)
+    c, t = C.case("end_to_end"), C.truth("end_to_end")
+    assert data.u.tobytes() == c.u.tobytes() and spec["sigma"] == c.sigma_u and rf.seeds == c.seeds
+    fine = nmrfit_amd.fit_replicas(data, spec["lower"], spec["upper"], replicas=8, sigma=spec["sigma"], seed=11,
+                                   options=dict(opts, polish=True))
+    assert np.all(fine.errors <= rf.errors) and np.array_equal(fine.iterations, rf.iterations)
+    b = C.bar(c)
+    pw = C.pointwise(t, fine.params[1:] - t.x0)
+    want = np.std(t.lin, axis=0, ddof=1)
+    af = np.array([C.area_fraction(t.x0 + d) for d in t.lin])
+    af_tol = C.spread_tolerance(1.01 * b * np.sum(np.abs(t.af_grad) * t.sigma_x), c.M)
+    print("end to end: polished, worst |D_k - D_lin,k| / sigma_x %.4f (bar %.4f); params_std / predicted: polished %s, "
+          "swarm alone %s; area_fraction_std: polished %.4e, swarm alone %.4e, predicted %.4e"
+          % (pw.max(), b, np.round(fine.params_std / want, 4), np.round(rf.params_std / want, 2), fine.area_fraction_std,
+             rf.area_fraction_std, np.std(af, ddof=1)))
+    assert np.all(pw <= b) and np.all(np.abs(fine.params[0] - t.x0) <= b * t.sigma_x)
+    assert np.all(np.abs(fine.params_std - want) <= C.spread_tolerance(b, c.M) * t.sigma_x)
+    assert abs(fine.area_fraction_std - np.std(af, ddof=1)) <= af_tol
     assert np.isfinite(rf.area_fraction_std) and rf.area_fraction_std > 0
     assert len({p.tobytes() for p in rf.params}) == 9                     # nine different fits
     assert data.u.tobytes() == u0.tobytes() and data.v.tobytes() == v0.tobytes()
