@@ -22,6 +22,8 @@ around it, behind the reference's own API for that path:
                                                                  a conditioned polynomial fit over a masked part of a grid)
     nmrfit_amd.correct_baseline_many(datas, deg=1)               a polynomial baseline fitted outside the peaks and taken out of V, I, u, v
     nmrfit_amd.fit_many(jobs, residual_baseline=1)               every fit carries fit.residual_baseline: the baseline of data_V - V
+    nmrfit_amd.fit_many(jobs, uncertainty=dict(sigma=s))         every fit carries fit.uncertainty: first-order standard errors of its
+                                                                 parameters and area fraction (the sandwich covariance, one launch)
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
@@ -33,7 +35,8 @@ bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
-from . import baseline, batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, utils  # noqa: F401
+from . import baseline, batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, uncertainty, utils  # noqa: F401
+from .uncertainty import FitUncertainty  # noqa: F401
 from .quality import FitQuality, residual_stats, residual_stats_many  # noqa: F401
 from .noise import fit_replicas, fit_replicas_many  # noqa: F401
 from .containers import Data, correct_baseline_many, select_peaks_many, shift_phase_many  # noqa: F401

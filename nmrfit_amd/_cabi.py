@@ -188,7 +188,14 @@ BASELINE_SIGNATURES = {
     "nmrfit_baseline_fit": [_INT, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_batch_residual_baseline": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
-LSQ_MAX_D = 76                   # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
+# COV_SIGNATURES: include/nmrfit_amd_cov.h (the sandwich covariance of a fit's parameters: A, the meat M, g and f from one
+# launch of the D + 1 residual rows, on a context or for every fit of a batch)
+_F64 = ctypes.c_double
+COV_SIGNATURES = {
+    "nmrfit_sandwich": [_VP, _I32, _VP, _VP, _F64, _F64, _F64, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_sandwich": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
+LSQ_MAX_D = 76                 # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
 _LIB = None
@@ -292,7 +299,7 @@ def lib():
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
                 + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
-                + list(BASELINE_SIGNATURES.items()):
+                + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -313,6 +313,57 @@ class FitBatch:
         return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), g[self.offsets[k]:self.offsets[k + 1]], float(f[k]))
                 for k in range(self.K)]
 
+    # -- sandwich covariance (include/nmrfit_amd_cov.h) ----------------------------------------------
+    def sandwich(self, X, sigma_u, sigma_v):
+        """Per fit ``(A, M, g, f)`` at the K parameter vectors ``X``, ONE call for the batch: ``normal_equations``'s A, g
+        and f (the same launches, bit for bit) and the meat M = J^T diag(q) J of the sandwich covariance (csrc/lsq_cov.hip),
+        q_j the variance of fit k's weighted residual under noise ``sigma_u[k]``, ``sigma_v[k]`` on its two channels
+        (scalars broadcast), from the batch's resident weights.  Bit-identical to
+        ``lsq.ResidualModel(Evaluator(spectrum), lower, upper).sandwich(X[k], ...)`` fit by fit, in any batch.  A batch
+        created with a ``fit_im`` mode is refused.  The swarms are not touched.  D <= 76 for every fit."""
+        from . import lsq
+        if len(X) != self.K:
+            raise ValueError("FitBatch.sandwich: one parameter vector per fit")
+        su = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.K,)))
+        sv = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (self.K,)))
+        rows, cs = [], []
+        s = 1.0 / np.sqrt(self.Ns.astype(np.float64))
+        for k, x in enumerate(X):
+            x = _cabi.f64(x)
+            if x.shape != (self.D[k],):
+                raise ValueError("FitBatch.sandwich: fit %d takes %d parameters" % (k, self.D[k]))
+            r, h = lsq.forward_rows(x, self.lowers[k], self.uppers[k])
+            rows.append(r.ravel())
+            cs.append(s[k] / h)
+        rows, cs = np.concatenate(rows), np.concatenate(cs)
+        D = np.asarray(self.D, dtype=np.int64)
+        aoff = np.concatenate(([0], np.cumsum(D * D)))
+        A, M = np.empty(int(aoff[-1])), np.empty(int(aoff[-1]))
+        g, f = np.empty(int(self.offsets[-1])), np.empty(self.K)
+        _cabi.check(self._lib.nmrfit_batch_sandwich(self._h, _cabi.ptr(rows), _cabi.ptr(cs), _cabi.ptr(s), _cabi.ptr(su),
+                                                    _cabi.ptr(sv), _cabi.ptr(A), _cabi.ptr(M), _cabi.ptr(g), _cabi.ptr(f)))
+        return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), M[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]),
+                 g[self.offsets[k]:self.offsets[k + 1]], float(f[k])) for k in range(self.K)]
+
+    def uncertainty(self, X=None, sigma_u=None, sigma_v=None):
+        """Per fit its ``uncertainty.FitUncertainty`` -- first-order standard errors of the parameters and of the
+        satellite area fraction, and the distance from the local minimiser in standard errors -- from one ``sandwich``
+        call and ``uncertainty.covariance`` per fit on the host.  ``X`` None: every fit's best position (``NmrfitError``
+        with the state code before the first generation).  ``sigma_u``, ``sigma_v``: the noise of the two channels, one
+        value or K; ``sigma_v`` None: ``sigma_u``'s."""
+        from . import uncertainty
+        if sigma_u is None:
+            raise ValueError("FitBatch.uncertainty: give sigma_u (and sigma_v): the noise of the two channels")
+        if sigma_v is None:
+            sigma_v = sigma_u
+        if X is None:
+            X = [x for x, _ in self.best()]
+        su = np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.K,))
+        sv = np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (self.K,))
+        got = self.sandwich(X, su, sv)
+        return [uncertainty.covariance(A, M, g, X[k], self.lowers[k], self.uppers[k], sigma=(float(su[k]), float(sv[k])))
+                for k, (A, M, g, _) in enumerate(got)]
+
     def polish(self, X=None, which=None, channels="real", **kwargs):
         """Least-squares refinement of the K fits in lock step (``lsq.lm_polish`` over ``normal_equations``): every
         launch evaluates the trial points of all fits still moving.  ``X`` None: from ``best()``.  ``which``: the fits

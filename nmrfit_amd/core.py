@@ -36,7 +36,7 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
 
 
 def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
-             batch_polish=False, quality=False, residual_baseline=None, **kwargs):
+             batch_polish=False, quality=False, residual_baseline=None, uncertainty=None, **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -115,13 +115,34 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       (those with ``options['polish']`` are refined before that), the fits that ran alone through ``generate_result``'s
       arrays and one ``baseline.fit_many`` call per device: the same V and data_V bits, the same rows.  ``params`` and
       ``error`` do not change and nothing is refitted: ``baseline.subtract_rotated`` and a second ``fit_many`` are the
-      recipe.  With ``shard=True`` the rows stay on the rank that made them."""
-    from . import baseline as _baseline
+      recipe.  With ``shard=True`` the rows stay on the rank that made them.
+    * ``uncertainty=dict(sigma=...)`` (a float or a pair (sigma_u, sigma_v)) or ``dict(noise_region=(xstart, xstop))``,
+      optionally with ``device_sigma=True`` -- exactly what they mean in ``fit_replicas_many``; a job's own ``sigma`` /
+      ``noise_region`` entry wins over the call's: every returned fit carries ``fit.uncertainty``
+      (``nmrfit_amd.uncertainty.FitUncertainty``): first-order standard errors of its FINAL ``params`` and of the
+      satellite area fraction from the sandwich covariance A^-1 M A^-1 (include/nmrfit_amd_cov.h, csrc/lsq_cov.hip) --
+      one launch of D + 1 residual rows per fit where ``fit_replicas`` runs 32 further fits -- and ``distance``, how many
+      standard errors ``params`` lies from the local minimiser: the errors describe the noise alone, and an unpolished
+      swarm stops 0.06 ... 76 of them away (ask for ``options['polish']``).  The fits of a device batch go through
+      ``FitBatch.uncertainty`` while the batch is resident (those with ``options['polish']`` are refined before that),
+      the fits that ran alone through a context (``FitUtility.uncertainty``).  Real channel only: a ``fit_im`` job raises
+      ValueError up front, so does one with more than 24 peaks.  ``params`` and ``error`` do not change.  With
+      ``shard=True`` the records stay on the rank that made them."""
+    from . import baseline as _baseline, uncertainty as _uncertainty
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
     call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights),
                  "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish), bool(quality),
-                 _baseline.option(residual_baseline))
+                 _baseline.option(residual_baseline), _uncertainty.option(uncertainty))
+    if call.uncertainty is not None:
+        from .equations import fit_im_mode
+        for m, job in enumerate(jobs):
+            args = dict(kwargs, **job)
+            if fit_im_mode(args.get("fit_im", False)):
+                raise ValueError("fit_many: uncertainty covers the real channel only: job %d has fit_im=%r" % (m, args["fit_im"]))
+            if len(args["lower"]) > _cabi.LSQ_MAX_D:
+                raise ValueError("fit_many: uncertainty takes fits of at most %d parameters (24 peaks): job %d has %d"
+                                 % (_cabi.LSQ_MAX_D, m, len(args["lower"])))
     if devices is not None:
         if shard:
             raise ValueError("fit_many: shard=True divides the jobs over PROCESSES, devices=[...] over the GPUs of this "
@@ -152,6 +173,7 @@ class _Call(typing.NamedTuple):
     batch_polish: object         # False, True (fit_im=False jobs), or "both" (the jobs of fit_im batches too, on both channels)
     quality: bool = False        # every fit gets ``quality``: its residual statistics per peak region (quality.py)
     residual_baseline: object = None   # None, or baseline.option()'s dict: every fit gets ``residual_baseline`` (baseline.py)
+    uncertainty: object = None   # None, or uncertainty.option()'s dict: every fit gets ``uncertainty`` (uncertainty.py)
 
 
 def _result_record(f):
@@ -169,8 +191,9 @@ def _merged_options(shared_options, job):
 
 def _fit_args(call, job):
     """``fit``'s arguments for one job: the call's keyword arguments, the job's own entries over them -- except
-    ``options``, which are merged key by key (``_merged_options``)."""
-    args = dict(call.kwargs, **job)
+    ``options``, which are merged key by key (``_merged_options``).  A job's ``sigma`` / ``noise_region`` are its noise
+    for ``call.uncertainty`` (``uncertainty.job_sigmas``), not arguments of ``fit``."""
+    args = {k: v for k, v in dict(call.kwargs, **job).items() if k not in ("sigma", "noise_region")}
     if "options" in call.kwargs or "options" in job:
         args["options"] = _merged_options(call.kwargs.get("options"), job)
     return args
@@ -282,6 +305,7 @@ class _Batch:
         self.fb, self.fits, self.plans, self.key, self.idx = fb, fits, plans, key, idx
         self.quality = None      # read(), ``call.quality``: the fits' FitQuality, made while the batch was resident
         self.residual_baseline = None      # read(), ``call.residual_baseline``: the fits' BaselineFit, likewise
+        self.uncertainty = None      # read(), ``call.uncertainty``: the fits' FitUncertainty, likewise
 
     @classmethod
     def create(cls, fits, plans, key, idx):
@@ -314,7 +338,8 @@ class _Batch:
         ``refined``: store leaves them alone.  ``call.quality``: the residual statistics of every fit at its final
         parameters, from the resident spectra (FitBatch.residual_stats) -- the fits store would refine one by one are
         refined here first and count as ``refined``.  ``call.residual_baseline``: the same for the polynomial baseline of
-        every fit's residual (FitBatch.residual_baseline).  Closes the batch.  Returns (refined, status, best, results)."""
+        every fit's residual (FitBatch.residual_baseline), ``call.uncertainty`` for the standard errors of every fit's
+        parameters under its own noise (FitBatch.uncertainty).  Closes the batch.  Returns (refined, status, best, results)."""
         fits, fb, refined = self.fits, self.fb, set()
         polished = sum(1 for f in fits if f.options.get('polish', False))
         try:
@@ -338,6 +363,10 @@ class _Batch:
             if call.residual_baseline is not None:
                 refined |= self._refine_per_fit(call, refined, best)
                 self.residual_baseline = _residual_baseline_resident(fb, call.residual_baseline, fits, [x for x, _ in best])
+            if call.uncertainty is not None:
+                refined |= self._refine_per_fit(call, refined, best)
+                self.uncertainty = fb.uncertainty([x for x, _ in best], [f.noise_sigma[0] for f in fits],
+                                                  [f.noise_sigma[1] for f in fits])
         finally:
             fb.close()
         return refined, status, best, results
@@ -378,6 +407,8 @@ class _Batch:
                 f.quality = self.quality[k]
             if self.residual_baseline is not None:
                 f.residual_baseline = self.residual_baseline[k]
+            if self.uncertainty is not None:
+                f.uncertainty = self.uncertainty[k]
             if k in polished:
                 if scale is not False:
                     f.generate_result(scale)      # (from the refined parameters: the batch's launch used the swarm's)
@@ -484,6 +515,13 @@ def _fit_many_local(jobs, call):
     for job in jobs:
         args = _fit_args(call, job)
         fits.append(utils.FitUtility(args.pop("data"), args.pop("lower"), args.pop("upper"), **args))
+    if call.uncertainty is not None:
+        # every fit's (sigma_u, sigma_v), before anything runs: a job without noise fails here, not after its fit
+        from . import uncertainty
+        device = int((call.kwargs.get("options") or {}).get("device") or 0)
+        for f, pair in zip(fits, uncertainty.job_sigmas([dict(job, data=f.data) for job, f in zip(jobs, fits)],
+                                                        call.uncertainty, device)):
+            f.noise_sigma = pair
     if not (call.batch and len(fits) > 1):
         return _fit_alone(fits, {}, range(len(fits)), call)
     n = len(fits)
@@ -559,4 +597,7 @@ def _fit_alone(fits, plans, alone, call):
             by_device.setdefault(fits[i]._device(), []).append(i)
         for device, idx in by_device.items():
             _residual_baseline_alone(fits, idx, call.residual_baseline, device)
+    if call.uncertainty is not None:
+        for i in alone:      # (a context per fit: the record takes the method's place on the fit)
+            fits[i].uncertainty = utils.FitUtility.uncertainty(fits[i], sigma=fits[i].noise_sigma)
     return fits

@@ -2,9 +2,12 @@
 // the residual rows, Jacobian sums and normal equations of every fit at the caller's points, on one channel or on both.
 // A part works through its fits in groups that fit the workspace budget (part_normal_equations, part_normal_group: the
 // launches are lsq.hip's); the batch hands every part its share of the caller's arrays (batch_normal_equations), and the
-// two nmrfit_batch_normal_equations* entry points differ in the channel count alone.  The swarms are not touched.
+// two nmrfit_batch_normal_equations* entry points differ in the channel count alone.  nmrfit_batch_sandwich
+// (include/nmrfit_amd_cov.h) is the real channel's call with a Meat: the same groups, one more pair of launches
+// (lsq_cov.hip) on the rows and factors the group has just used.  The swarms are not touched.
 #include "batch_part.h"
 #include "lsq_internal.h"
+#include "nmrfit_amd_cov.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -13,6 +16,13 @@
 
 using namespace nmrfit;
 
+// What nmrfit_batch_sandwich adds to a normal-equations call: the two channels' noise of every fit (K values each, like
+// s) and where the meats go (laid out like A).  A part, then a group, sees its own share.
+struct Meat {
+    const double *sigma_u, *sigma_v;
+    double *M_out;
+};
+
 // include/nmrfit_amd_lsq.h for the fits [k0, k1) of a part: their residual rows in ONE launch over the part's resident
 // spectra (lsq.hip, residual_rows_batch_kernel), J tile by tile and the segments' sums in a second, the ordered sums in
 // a third.  rows, c, s and the outputs point at fit k0's share.  Everything the call allocates goes with `mem` on every
@@ -20,7 +30,8 @@ using namespace nmrfit;
 // fit_im 1 or 2 (include/nmrfit_amd_lsq_im.h): rows of both channels -- nch = 2 planes of residual rows per fit, two jobs
 // per fit (real, imaginary) in the same launches, and per fit [2][D x D] of A, [2][D] of g, the pair (rho_re, rho_im) of f.
 static int part_normal_group(BatchPart *b, int32_t k0, int32_t k1, size_t lds, unsigned aux_off, const double *rows, const double *c,
-                             const double *s, double *A_out, double *g_out, double *f_out, Scratch &mem, int fit_im)
+                             const double *s, double *A_out, double *g_out, double *f_out, Scratch &mem, int fit_im,
+                             const Meat *meat = nullptr)
 {
     const int32_t Kg = k1 - k0;
     const bool sums = A_out || g_out;
@@ -105,6 +116,46 @@ static int part_normal_group(BatchPart *b, int32_t k0, int32_t k1, size_t lds, u
     int rc = launch_rows_batch(st, d_fits, Kg, Smax, lds, aux_off, fit_im);
     if (rc != NMRFIT_OK) return rc;
     if (sums && (rc = launch_lsq(st, d_jobs, nch * Kg, Dmax, true)) != NMRFIT_OK) return rc;
+    if (meat && meat->M_out) {
+        // the meat of every fit (real channel alone: job k - k0 is fit k's): R and c where the fit's LsqJob has them, the
+        // fit's resident weights, the phase of its row 0; one more block of `mem`: [records | segments' sums | M]
+        int64_t n_mpartial = 0;
+        for (int32_t k = k0; k < k1; ++k) n_mpartial += jobs[k - k0].nseg * (lsq_sums(b->D[(size_t)k]) - b->D[(size_t)k]);
+        const int64_t n_M = n_rows - n_c;   // sum of D^2
+        const size_t mrec = align256((size_t)Kg * sizeof(LsqMeatJob)) / sizeof(double);
+        double *d_meat = nullptr;
+        NMRFIT_HIP(mem.alloc(&d_meat, mrec + (size_t)(n_mpartial + n_M)));
+        double *d_mpartial = d_meat + mrec, *d_M = d_mpartial + n_mpartial;
+        std::vector<LsqMeatJob> mjobs((size_t)Kg);
+        int64_t at_mp = 0, at_M = 0, at_x = 0;
+        for (int32_t k = k0; k < k1; ++k) {
+            const LsqJob &j = jobs[k - k0];
+            const int64_t D = j.D;
+            LsqMeatJob &m = mjobs[(size_t)(k - k0)];
+            m = LsqMeatJob{};
+            m.R = j.R;
+            m.c = j.c;
+            m.wt = b->h_fits[(size_t)k].wt;
+            m.s = j.s;
+            m.p0 = rows[at_x];
+            m.p1 = rows[at_x + 1];
+            m.var_u = meat->sigma_u[k - k0] * meat->sigma_u[k - k0];
+            m.var_v = meat->sigma_v[k - k0] * meat->sigma_v[k - k0];
+            m.N = j.N;
+            m.D = j.D;
+            m.nseg = j.nseg;
+            m.seg_tiles = j.seg_tiles;
+            m.partial = d_mpartial + at_mp;
+            m.M = d_M + at_M;
+            at_mp += j.nseg * (lsq_sums(D) - D);
+            at_M += D * D;
+            at_x += (D + 1) * D;
+        }
+        // (pageable host memory: the copy has left `mjobs` when hipMemcpyAsync returns)
+        NMRFIT_HIP(hipMemcpyAsync(d_meat, mjobs.data(), mjobs.size() * sizeof(LsqMeatJob), hipMemcpyHostToDevice, st));
+        if ((rc = launch_lsq_meat(st, reinterpret_cast<const LsqMeatJob *>(d_meat), Kg, Dmax)) != NMRFIT_OK) return rc;
+        NMRFIT_HIP(hipMemcpyAsync(meat->M_out, d_M, (size_t)n_M * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     if (A_out) NMRFIT_HIP(hipMemcpyAsync(A_out, d_A, (size_t)n_A * sizeof(double), hipMemcpyDeviceToHost, st));
     if (g_out) NMRFIT_HIP(hipMemcpyAsync(g_out, d_g, (size_t)(nch * n_c) * sizeof(double), hipMemcpyDeviceToHost, st));
     std::vector<double> fall(f_out ? (size_t)n_f : 0);
@@ -120,7 +171,7 @@ static int part_normal_group(BatchPart *b, int32_t k0, int32_t k1, size_t lds, u
 
 
 static int part_normal_equations(BatchPart *b, const double *rows, const double *c, const double *s, double *A_out, double *g_out,
-                                 double *f_out, int fit_im)
+                                 double *f_out, int fit_im, const Meat *meat = nullptr)
 {
     const int nch = fit_im ? 2 : 1;
     int rc = bind_batch(b);
@@ -153,8 +204,11 @@ static int part_normal_equations(BatchPart *b, const double *rows, const double 
         }
         {
             Scratch mem;
+            const Meat group{meat ? meat->sigma_u + k0 : nullptr, meat ? meat->sigma_v + k0 : nullptr,
+                             meat && meat->M_out ? meat->M_out + at_A : nullptr};
             rc = part_normal_group(b, k0, k1, lds, aux_off, rows + at_rows, c + at_c, s + k0, A_out ? A_out + at_A : nullptr,
-                                   g_out ? g_out + nch * at_c : nullptr, f_out ? f_out + nch * k0 : nullptr, mem, fit_im);
+                                   g_out ? g_out + nch * at_c : nullptr, f_out ? f_out + nch * k0 : nullptr, mem, fit_im,
+                                   meat ? &group : nullptr);
             if (rc != NMRFIT_OK) (void)hipStreamSynchronize(b->stream);   // what was enqueued may still use the buffers `mem` frees
         }
         at_rows += d_rows;
@@ -168,16 +222,18 @@ static int part_normal_equations(BatchPart *b, const double *rows, const double 
 // Both entry points: a part's share of every array starts where the fits before it end -- rows [(D + 1) x D], c [D] and
 // s [1] per fit, and nch channels of A [D x D], g [D] and f [1] (nch = 2: the batch's own fit_im says which imaginary model)
 static int batch_normal_equations(nmrfit_batch *b, const char *who, int nch, const double *rows, const double *c, const double *s,
-                                  double *A_out, double *g_out, double *f_out)
+                                  double *A_out, double *g_out, double *f_out, const Meat *meat = nullptr)
 {
     int rc = check_idle(b, who);
     int64_t at_rows = 0, at_A = 0;
     for (size_t p = 0; p < b->parts.size() && rc == NMRFIT_OK; ++p) {
         const int32_t f0 = b->first[p], f1 = b->first[p + 1];
         const int64_t at_c = b->boff[(size_t)f0];
+        const Meat part{meat ? meat->sigma_u + f0 : nullptr, meat ? meat->sigma_v + f0 : nullptr,
+                        meat && meat->M_out ? meat->M_out + at_A : nullptr};
         rc = part_normal_equations(b->parts[p], rows + at_rows, c + at_c, s + f0, A_out ? A_out + nch * at_A : nullptr,
                                    g_out ? g_out + nch * at_c : nullptr, f_out ? f_out + nch * f0 : nullptr,
-                                   nch == 2 ? b->parts[p]->fit_im : 0);
+                                   nch == 2 ? b->parts[p]->fit_im : 0, meat ? &part : nullptr);
         for (int32_t k = f0; k < f1; ++k) {
             const int64_t D = b->boff[(size_t)k + 1] - b->boff[(size_t)k];
             at_rows += (D + 1) * D;
@@ -212,6 +268,27 @@ int nmrfit_batch_normal_equations_im(nmrfit_batch *b, const double *rows, const 
         return NMRFIT_E_INVALID;
     }
     return batch_normal_equations(b, "nmrfit_batch_normal_equations_im", 2, rows, c, s, A_out, g_out, f2_out);
+}
+
+// include/nmrfit_amd_cov.h.  Every refusal comes before the first launch: the batch is as it was.
+int nmrfit_batch_sandwich(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
+                          const double *sigma_v, double *A_out, double *M_out, double *g_out, double *f_out)
+{
+    int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    if (!rows || !c || !s || !sigma_u || !sigma_v)
+        return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich: null rows, c, s, sigma_u or sigma_v");
+    for (int32_t k = 0; k < b->K; ++k)
+        if ((rc = check_sigma("nmrfit_batch_sandwich", sigma_u[k], sigma_v[k])) != NMRFIT_OK) return rc;
+    for (const BatchPart *p : b->parts) {
+        if (p->fit_im != NMRFIT_FIT_IM_OFF)
+            return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich: the batch was created with a fit_im mode: its fits minimise "
+                                                "a mean of two norms, which this covariance does not describe");
+        if (4 + 3 * (int64_t)p->Pmax > kLsqMaxD)
+            return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich: D = 4 + 3 P <= " + std::to_string(kLsqMaxD) + " for every fit");
+    }
+    const Meat meat{sigma_u, sigma_v, M_out};
+    return batch_normal_equations(b, "nmrfit_batch_sandwich", 1, rows, c, s, A_out, g_out, f_out, &meat);
 }
 
 }  // extern "C"

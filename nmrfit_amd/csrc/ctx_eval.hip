@@ -191,7 +191,7 @@ int nmrfit_residual_batch_im(nmrfit_ctx *ctx, int64_t B, int32_t P, const double
 // device; what comes back is J in scipy's layout, r, and / or the D x D normal equations, per channel.  One upload (rows, c,
 // the kernels' records), the rows launch, the kernels of lsq.hip -- a channel is one job of theirs, on its plane of the
 // rows -- and the copies back (J and r through the pinned staging buffers).  The workspace is [J, r, partial, A, g] per
-// channel; every output has the channel as its leading index, and f is the nch RMSEs of row 0.
+// channel; every output has the channel as its leading index, f is the nch RMSEs of row 0.  (R stays in d_R and c behind the rows in d_X: nmrfit_sandwich, lsq_cov.hip, reads them there.)
 static int ctx_jacobian(nmrfit_ctx *ctx, const char *who, int nch, int fit_im, int32_t P, const double *rows, const double *c,
                         double s, double *J_out, double *r_out, double *A_out, double *g_out, double *f_out)
 {

@@ -25,24 +25,6 @@
 namespace nmrfit {
 namespace {
 
-// entry o of a fit's sums -> the pair (a, b): the upper triangle row after row, then the D entries of g as (i, D)
-__device__ __forceinline__ void lsq_pair(int o, int D, int *a, int *b)
-{
-    const int ntri = D * (D + 1) / 2;
-    if (o >= ntri) {
-        *a = o - ntri;
-        *b = D;
-        return;
-    }
-    int row = 0, rem = o;
-    while (rem >= D - row) {
-        rem -= D - row;
-        ++row;
-    }
-    *a = row;
-    *b = row + rem;
-}
-
 __global__ __launch_bounds__(kLsqThreads) void lsq_normal_kernel(const LsqJob *__restrict__ jobs)
 {
     extern __shared__ double T[];   // [kLsqTile][pitch]

@@ -1,5 +1,6 @@
-// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), ctx_eval.hip (nmrfit_jacobian*) and
-// batch_lsq.hip (nmrfit_batch_normal_equations*): the per-fit records the kernels read and the launches.
+// lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), lsq_cov.hip (those of
+// include/nmrfit_amd_cov.h, nmrfit_sandwich), ctx_eval.hip (nmrfit_jacobian*) and batch_lsq.hip
+// (nmrfit_batch_normal_equations*, nmrfit_batch_sandwich): the per-fit records the kernels read and the launches.
 #pragma once
 #include "nmrfit_amd_lsq.h"
 #include "nmrfit_amd_lsq_im.h"
@@ -41,8 +42,46 @@ inline void lsq_segments(int64_t N, int32_t *nseg, int32_t *seg_tiles)
 }
 inline int64_t lsq_sums(int64_t D) { return D * (D + 1) / 2 + D; }
 
+// entry o of a fit's sums -> the pair (a, b): the upper triangle row after row, then the D entries of g as (i, D)
+__device__ __forceinline__ void lsq_pair(int o, int D, int *a, int *b)
+{
+    const int ntri = D * (D + 1) / 2;
+    if (o >= ntri) {
+        *a = o - ntri;
+        *b = D;
+        return;
+    }
+    int row = 0, rem = o;
+    while (rem >= D - row) {
+        rem -= D - row;
+        ++row;
+    }
+    *a = row;
+    *b = row + rem;
+}
+
 // J, r and -- where a job has `partial` -- A and g of K fits (jobs: device memory), on `st`.  Dmax <= kLsqMaxD.
 int launch_lsq(hipStream_t st, const LsqJob *d_jobs, int32_t K, int32_t Dmax, bool sums);
+
+// One fit of a meat launch (lsq_cov.hip, include/nmrfit_amd_cov.h): R and c as its LsqJob has them, the fit's resident
+// weights (grid_slot order, padded to whole chunks), the phase of row 0 and the two channels' noise variances.
+struct LsqMeatJob {
+    const double *R;
+    const double *c;
+    const double *wt;
+    double s, p0, p1;
+    double var_u, var_v;   // sigma_u^2, sigma_v^2
+    int64_t N;
+    int32_t D;
+    int32_t nseg, seg_tiles;   // lsq_segments(N)
+    int32_t pad;
+    double *partial;       // nseg x D (D + 1) / 2
+    double *M;             // D x D
+};
+// M = J^T diag(q) J of K fits (jobs: device memory), on `st`, after the rows launch that made every R.  Dmax <= kLsqMaxD.
+int launch_lsq_meat(hipStream_t st, const LsqMeatJob *d_jobs, int32_t K, int32_t Dmax);
+// NMRFIT_E_INVALID unless both are finite and >= 0
+int check_sigma(const char *who, double sigma_u, double sigma_v);
 // J and r alone for one fit of any D (no LDS tile): what nmrfit_jacobian runs beyond kLsqMaxD
 int launch_lsq_plain(hipStream_t st, const LsqJob &job);
 

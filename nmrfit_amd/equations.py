@@ -198,6 +198,21 @@ class Evaluator:
         the objective value of row 0."""
         return self._jacobian("jacobian", False, None, rows, c, s, J, r, normal)
 
+    def sandwich(self, rows, c, s, sigma_u, sigma_v):
+        """``nmrfit_sandwich`` (include/nmrfit_amd_cov.h): a dict with ``A`` = J^T J, ``M`` = J^T diag(q) J -- q_j the
+        variance of the weighted residual at grid point j under noise (sigma_u, sigma_v) on the two channels, from the
+        context's weights and the phase of row 0 -- ``g`` = J^T r [D] and ``f``; A, g and f are ``jacobian``'s bit for
+        bit.  ``uncertainty.covariance`` makes standard errors of them.  DEFAULT kernel variant, D <= 76."""
+        rows, P = self._as_batch(rows)
+        D = rows.shape[1]
+        c = _cabi.f64(c)
+        if rows.shape[0] != D + 1 or c.shape != (D,):
+            raise ValueError("sandwich: rows must be (D + 1) x D and c have D entries")
+        A, M, g, f = np.empty((D, D)), np.empty((D, D)), np.empty(D), np.empty(1)
+        _cabi.check(self._lib.nmrfit_sandwich(self._ctx, P, _cabi.ptr(rows), _cabi.ptr(c), float(s), float(sigma_u),
+                                              float(sigma_v), _cabi.ptr(A), _cabi.ptr(M), _cabi.ptr(g), _cabi.ptr(f)))
+        return dict(A=A, M=M, g=g, f=float(f[0]))
+
     # -- both channels (include/nmrfit_amd_lsq_im.h) -------------------------------------------
     def residual_batch_im(self, X, fit_im):
         """``(R_re, R_im, f2)``: the residual rows of both channels of the parameter rows ``X`` -- R_re what

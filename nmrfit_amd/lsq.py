@@ -158,6 +158,17 @@ class ResidualModel:
         out = self.ev.jacobian(rows, self._scale / h, self._scale, normal=True)
         return out["A"], out["g"], out["f"]
 
+    def sandwich(self, x, sigma_u, sigma_v):
+        """``(A, M, g, f)`` at x: ``normal_equations``'s A, g and f (the same launches, the same bits) and the meat
+        M = J^T diag(q) J of the sandwich covariance under noise (sigma_u, sigma_v) on the two channels
+        (``Evaluator.sandwich``; ``uncertainty.covariance`` takes them).  Real channel only, D <= 76."""
+        if self.fit_im:
+            raise ValueError("ResidualModel.sandwich: the covariance covers the real channel only (fit_im=False)")
+        self.n_jac += 1
+        rows, h = self.rows(x)
+        out = self.ev.sandwich(rows, self._scale / h, self._scale, sigma_u, sigma_v)
+        return out["A"], out["M"], out["g"], out["f"]
+
     def objective(self, x):
         return float(np.linalg.norm(self.fun(x)))
 

@@ -472,6 +472,30 @@ class FitUtility:
                                               device=self._device())
         return self.quality
 
+    def uncertainty(self, sigma=None, noise_region=None):
+        """The ``uncertainty.FitUncertainty`` of this finished fit at ``params``: first-order standard errors of the
+        parameters and of the satellite area fraction from ONE launch of the D + 1 residual rows on a context
+        (nmrfit_sandwich, csrc/lsq_cov.hip) -- the sandwich A^-1 M A^-1, not sigma^2 (J^T J)^-1 / N: the weights are not
+        1/sigma -- and ``distance``, how many of them ``params`` lies from the local minimiser (large after an unpolished
+        swarm).  ``sigma``: the noise of the spectrum, a float or a pair (sigma_u, sigma_v); else
+        ``noise_region=(xstart, xstop)``, a signal-free stretch -- as ``fit_replicas`` takes them.  Real channel only
+        (``fit_im=False``), at most 24 peaks.  The record is returned, not kept: on the fits that
+        ``fit_many(uncertainty=...)`` returns, the attribute ``uncertainty`` IS their record (it stands in this method's
+        place there)."""
+        from . import lsq, noise, uncertainty
+        if 'params' not in self.__dict__:      # (not hasattr: __getattr__ answers for missing names)
+            raise AttributeError("uncertainty: this fit has no params yet (call fit() first)")
+        if equations.fit_im_mode(self.fit_im):
+            raise ValueError("uncertainty: the covariance covers the real channel only (fit_im=False)")
+        su, sv = noise._job_sigma(dict(sigma=sigma, noise_region=noise_region), self.data)
+        lower, upper = _cabi.f64(self.lower), _cabi.f64(self.upper)
+        ev = equations.Evaluator(self.data.w, self.data.u, self.data.v, self.weights, device=self._device())
+        try:
+            A, M, g, _ = lsq.ResidualModel(ev, lower, upper).sandwich(self.params, su, sv)
+        finally:
+            ev.close()
+        return uncertainty.covariance(A, M, g, self.params, lower, upper, sigma=(su, sv))
+
     def residual_arrays(self):
         """``data_V - V`` of this finished fit on its own grid, from the arrays of ``generate_result`` (one launch of the
         reconstruction kernel: the bits a device batch's ``residual_baseline`` works on); nothing is stored."""
