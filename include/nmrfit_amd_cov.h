@@ -18,7 +18,8 @@
  * sums over whole tiles of NMRFIT_LSQ_TILE points, then the segments one after the other, both triangles written from
  * one sum): the same inputs give the same bits on every run, on a context or anywhere in any batch.  No atomics.
  * The weights are the resident ones (the context's, the batch's); q_j is formed in fp64 on the device.
- * Real channel only: a fit made with fit_im minimises a mean of two norms, and is refused.
+ * Real channel only: a fit made with fit_im minimises a mean of two norms, and is refused here (its entrance is
+ * nmrfit_amd_cov_im.h: nmrfit_sandwich_im, nmrfit_batch_sandwich_im).
  * D = 4 + 3 P <= NMRFIT_LSQ_MAX_D, else NMRFIT_E_UNSUPPORTED.  sigma_u, sigma_v: finite and >= 0, else NMRFIT_E_INVALID.
  */
 #ifndef NMRFIT_AMD_COV_H

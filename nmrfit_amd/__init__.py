@@ -24,6 +24,8 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.fit_many(jobs, residual_baseline=1)               every fit carries fit.residual_baseline: the baseline of data_V - V
     nmrfit_amd.fit_many(jobs, uncertainty=dict(sigma=s))         every fit carries fit.uncertainty: first-order standard errors of its
                                                                  parameters and area fraction (the sandwich covariance, one launch)
+    nmrfit_amd.fit_many(jobs, fit_im="sum", batch_polish="both", uncertainty=dict(sigma=s, channels="both"))
+                                                                 the same for fit_im fits: the two-channel sandwich
 
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when

@@ -195,6 +195,12 @@ COV_SIGNATURES = {
     "nmrfit_sandwich": [_VP, _I32, _VP, _VP, _F64, _F64, _F64, _VP, _VP, _VP, _VP],
     "nmrfit_batch_sandwich": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# COV_IM_SIGNATURES: include/nmrfit_amd_cov_im.h (the same for a fit made on both channels: A, g and rho per channel and
+# the three blocks of the two-channel meat)
+COV_IM_SIGNATURES = {
+    "nmrfit_sandwich_im": [_VP, _I32, _INT, _VP, _VP, _F64, _F64, _F64, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_sandwich_im": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                 # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -299,7 +305,7 @@ def lib():
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
                 + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
-                + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()):
+                + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -320,7 +320,7 @@ class FitBatch:
         q_j the variance of fit k's weighted residual under noise ``sigma_u[k]``, ``sigma_v[k]`` on its two channels
         (scalars broadcast), from the batch's resident weights.  Bit-identical to
         ``lsq.ResidualModel(Evaluator(spectrum), lower, upper).sandwich(X[k], ...)`` fit by fit, in any batch.  A batch
-        created with a ``fit_im`` mode is refused.  The swarms are not touched.  D <= 76 for every fit."""
+        created with a ``fit_im`` mode is refused (``sandwich_im`` is its call).  The swarms are not touched.  D <= 76 for every fit."""
         from . import lsq
         if len(X) != self.K:
             raise ValueError("FitBatch.sandwich: one parameter vector per fit")
@@ -345,13 +345,57 @@ class FitBatch:
         return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), M[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]),
                  g[self.offsets[k]:self.offsets[k + 1]], float(f[k])) for k in range(self.K)]
 
-    def uncertainty(self, X=None, sigma_u=None, sigma_v=None):
+    def sandwich_im(self, X, sigma_u, sigma_v):
+        """Per fit ``(parts, meat)`` at the K parameter vectors ``X`` of a batch created with a ``fit_im`` mode, ONE call
+        for the batch (nmrfit_batch_sandwich_im): ``parts`` the channels' ``(A_ch, g_ch, rho_ch)`` --
+        ``normal_equations(channels="both")``'s launches, bit for bit -- and ``meat`` [3, D + 1, D + 1] the blocks
+        (rr, ii, ri) of the two-channel sandwich (csrc/lsq_cov_im.hip) under noise ``sigma_u[k]``, ``sigma_v[k]`` (scalars
+        broadcast), from the batch's resident weights.  Bit-identical to
+        ``lsq.ResidualModel(Evaluator(spectrum), lower, upper, fit_im=mode).sandwich_im(X[k], ...)`` fit by fit, in any
+        batch.  The swarms are not touched.  D <= 76 for every fit."""
+        from . import lsq
+        if len(X) != self.K:
+            raise ValueError("FitBatch.sandwich_im: one parameter vector per fit")
+        su = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.K,)))
+        sv = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (self.K,)))
+        rows, cs = [], []
+        s = 1.0 / np.sqrt(self.Ns.astype(np.float64))
+        for k, x in enumerate(X):
+            x = _cabi.f64(x)
+            if x.shape != (self.D[k],):
+                raise ValueError("FitBatch.sandwich_im: fit %d takes %d parameters" % (k, self.D[k]))
+            r, h = lsq.forward_rows(x, self.lowers[k], self.uppers[k])
+            rows.append(r.ravel())
+            cs.append(s[k] / h)
+        rows, cs = np.concatenate(rows), np.concatenate(cs)
+        D = np.asarray(self.D, dtype=np.int64)
+        aoff = np.concatenate(([0], np.cumsum(D * D)))
+        moff = np.concatenate(([0], np.cumsum(3 * (D + 1) * (D + 1))))
+        A2, g2, f2 = np.empty(2 * int(aoff[-1])), np.empty(2 * int(self.offsets[-1])), np.empty(2 * self.K)
+        M = np.empty(int(moff[-1]))
+        _cabi.check(self._lib.nmrfit_batch_sandwich_im(self._h, _cabi.ptr(rows), _cabi.ptr(cs), _cabi.ptr(s), _cabi.ptr(su),
+                                                       _cabi.ptr(sv), _cabi.ptr(A2), _cabi.ptr(g2), _cabi.ptr(f2), _cabi.ptr(M)))
+        out = []
+        for k in range(self.K):
+            d = self.D[k]
+            Ak = A2[2 * aoff[k]:2 * aoff[k + 1]].reshape(2, d, d)
+            gk = g2[2 * self.offsets[k]:2 * self.offsets[k + 1]].reshape(2, d)
+            out.append(([(Ak[ch], gk[ch], float(f2[2 * k + ch])) for ch in (0, 1)], M[moff[k]:moff[k + 1]].reshape(3, d + 1, d + 1)))
+        return out
+
+    def uncertainty(self, X=None, sigma_u=None, sigma_v=None, channels="real"):
         """Per fit its ``uncertainty.FitUncertainty`` -- first-order standard errors of the parameters and of the
         satellite area fraction, and the distance from the local minimiser in standard errors -- from one ``sandwich``
         call and ``uncertainty.covariance`` per fit on the host.  ``X`` None: every fit's best position (``NmrfitError``
         with the state code before the first generation).  ``sigma_u``, ``sigma_v``: the noise of the two channels, one
-        value or K; ``sigma_v`` None: ``sigma_u``'s."""
+        value or K; ``sigma_v`` None: ``sigma_u``'s.
+
+        ``channels="both"`` (a batch created with a ``fit_im`` mode): one ``sandwich_im`` call and
+        ``uncertainty.covariance_im`` per fit.  The errors belong to the minimiser of f = (rho_re + rho_im)/2, and
+        ``distance`` is measured with grad f: ``polish(channels="both")`` is the polish that reaches that minimiser."""
         from . import uncertainty
+        if channels not in ("real", "both"):
+            raise ValueError('FitBatch.uncertainty: channels is "real" or "both"')
         if sigma_u is None:
             raise ValueError("FitBatch.uncertainty: give sigma_u (and sigma_v): the noise of the two channels")
         if sigma_v is None:
@@ -360,6 +404,10 @@ class FitBatch:
             X = [x for x, _ in self.best()]
         su = np.broadcast_to(np.asarray(sigma_u, dtype=np.float64), (self.K,))
         sv = np.broadcast_to(np.asarray(sigma_v, dtype=np.float64), (self.K,))
+        if channels == "both":
+            return [uncertainty.covariance_im(parts, meat, X[k], self.lowers[k], self.uppers[k],
+                                              sigma=(float(su[k]), float(sv[k])))
+                    for k, (parts, meat) in enumerate(self.sandwich_im(X, su, sv))]
         got = self.sandwich(X, su, sv)
         return [uncertainty.covariance(A, M, g, X[k], self.lowers[k], self.uppers[k], sigma=(float(su[k]), float(sv[k])))
                 for k, (A, M, g, _) in enumerate(got)]

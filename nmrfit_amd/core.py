@@ -126,8 +126,13 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       swarm stops 0.06 ... 76 of them away (ask for ``options['polish']``).  The fits of a device batch go through
       ``FitBatch.uncertainty`` while the batch is resident (those with ``options['polish']`` are refined before that),
       the fits that ran alone through a context (``FitUtility.uncertainty``).  Real channel only: a ``fit_im`` job raises
-      ValueError up front, so does one with more than 24 peaks.  ``params`` and ``error`` do not change.  With
-      ``shard=True`` the records stay on the rank that made them."""
+      ValueError up front -- unless the dict says ``channels="both"``, see below -- so does one with more than 24 peaks.
+      ``params`` and ``error`` do not change.  With ``shard=True`` the records stay on the rank that made them.
+    * ``uncertainty=dict(..., channels="both")``: the ``fit_im`` jobs of the call get the two-channel record
+      (include/nmrfit_amd_cov_im.h, csrc/lsq_cov_im.hip; ``uncertainty.covariance_im``) while their batch is resident,
+      after any polish; the ``fit_im=False`` jobs of the same call get the record they always got, bit for bit.  The
+      errors of a ``fit_im`` fit belong to the minimiser of f = (rho_re + rho_im)/2 and ``distance`` is measured with
+      grad f: ``batch_polish="both"`` is the polish that reaches that minimiser."""
     from . import baseline as _baseline, uncertainty as _uncertainty
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
@@ -138,7 +143,7 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
         from .equations import fit_im_mode
         for m, job in enumerate(jobs):
             args = dict(kwargs, **job)
-            if fit_im_mode(args.get("fit_im", False)):
+            if fit_im_mode(args.get("fit_im", False)) and call.uncertainty.get("channels", "real") != "both":
                 raise ValueError("fit_many: uncertainty covers the real channel only: job %d has fit_im=%r" % (m, args["fit_im"]))
             if len(args["lower"]) > _cabi.LSQ_MAX_D:
                 raise ValueError("fit_many: uncertainty takes fits of at most %d parameters (24 peaks): job %d has %d"
@@ -365,8 +370,10 @@ class _Batch:
                 self.residual_baseline = _residual_baseline_resident(fb, call.residual_baseline, fits, [x for x, _ in best])
             if call.uncertainty is not None:
                 refined |= self._refine_per_fit(call, refined, best)
+                # (a batch has one fit_im mode: fit_many has refused such jobs unless the call says channels="both")
+                kw = dict(channels="both") if any(f.fit_im for f in fits) else {}
                 self.uncertainty = fb.uncertainty([x for x, _ in best], [f.noise_sigma[0] for f in fits],
-                                                  [f.noise_sigma[1] for f in fits])
+                                                  [f.noise_sigma[1] for f in fits], **kw)
         finally:
             fb.close()
         return refined, status, best, results
@@ -599,5 +606,6 @@ def _fit_alone(fits, plans, alone, call):
             _residual_baseline_alone(fits, idx, call.residual_baseline, device)
     if call.uncertainty is not None:
         for i in alone:      # (a context per fit: the record takes the method's place on the fit)
-            fits[i].uncertainty = utils.FitUtility.uncertainty(fits[i], sigma=fits[i].noise_sigma)
+            fits[i].uncertainty = utils.FitUtility.uncertainty(fits[i], sigma=fits[i].noise_sigma,
+                                                               channels=call.uncertainty.get("channels", "real"))
     return fits

@@ -4,10 +4,13 @@
 // launches are lsq.hip's); the batch hands every part its share of the caller's arrays (batch_normal_equations), and the
 // two nmrfit_batch_normal_equations* entry points differ in the channel count alone.  nmrfit_batch_sandwich
 // (include/nmrfit_amd_cov.h) is the real channel's call with a Meat: the same groups, one more pair of launches
-// (lsq_cov.hip) on the rows and factors the group has just used.  The swarms are not touched.
+// (lsq_cov.hip) on the rows and factors the group has just used; nmrfit_batch_sandwich_im (include/nmrfit_amd_cov_im.h)
+// is the both-channel call with one: four jobs per fit of lsq_cov_im.hip's launches (group_meat_im).  The swarms are not
+// touched.
 #include "batch_part.h"
 #include "lsq_internal.h"
 #include "nmrfit_amd_cov.h"
+#include "nmrfit_amd_cov_im.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -17,11 +20,50 @@
 using namespace nmrfit;
 
 // What nmrfit_batch_sandwich adds to a normal-equations call: the two channels' noise of every fit (K values each, like
-// s) and where the meats go (laid out like A).  A part, then a group, sees its own share.
+// s) and where the meats go (laid out like A; both channels: [3][C x C] per fit, C = D + 1).  A part, then a group, sees
+// its own share.
 struct Meat {
     const double *sigma_u, *sigma_v;
     double *M_out;
 };
+// doubles of M_out one fit of D parameters takes
+static int64_t meat_doubles(int64_t D, int nch) { return nch == 2 ? 3 * (D + 1) * (D + 1) : D * D; }
+
+// The two-channel meat of the fits [k0, k1) of a group (lsq_cov_im.hip): jobs are the group's LsqJobs, two per fit (real,
+// imaginary), whose R and c the four meat jobs of the fit read; rows the group's parameter rows (the phase of row 0).
+// One more block of `mem`: [records | segments' sums | M].
+static int group_meat_im(BatchPart *b, int32_t k0, int32_t k1, const LsqJob *jobs, const double *rows, const Meat &meat,
+                         int32_t Dmax, Scratch &mem)
+{
+    const int32_t Kg = k1 - k0;
+    int64_t n_partial = 0, n_M = 0;
+    for (int32_t k = k0; k < k1; ++k) {
+        n_partial += lsq_meat_im_partials(b->Nk[(size_t)k], b->D[(size_t)k]);
+        n_M += meat_doubles(b->D[(size_t)k], 2);
+    }
+    const size_t mrec = align256((size_t)Kg * 4 * sizeof(LsqMeatImJob)) / sizeof(double);
+    double *d_meat = nullptr;
+    NMRFIT_HIP(mem.alloc(&d_meat, mrec + (size_t)(n_partial + n_M)));
+    double *d_partial = d_meat + mrec, *d_M = d_partial + n_partial;
+    std::vector<LsqMeatImJob> mjobs((size_t)Kg * 4);
+    int64_t at_p = 0, at_M = 0, at_x = 0;
+    for (int32_t k = k0; k < k1; ++k) {
+        const LsqJob &j = jobs[2 * (k - k0)];   // (the real channel's: its R is the first of the fit's two planes)
+        const int64_t D = j.D;
+        lsq_meat_im_jobs(&mjobs[(size_t)(k - k0) * 4], j.R, j.c, b->h_fits[(size_t)k].wt, j.s, rows[at_x], rows[at_x + 1],
+                         meat.sigma_u[k - k0], meat.sigma_v[k - k0], j.N, j.D, d_partial + at_p, d_M + at_M);
+        at_p += lsq_meat_im_partials(j.N, D);
+        at_M += meat_doubles(D, 2);
+        at_x += (D + 1) * D;
+    }
+    hipStream_t st = b->stream;
+    // (pageable host memory: the copy has left `mjobs` when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(d_meat, mjobs.data(), mjobs.size() * sizeof(LsqMeatImJob), hipMemcpyHostToDevice, st));
+    const int rc = launch_lsq_meat_im(st, reinterpret_cast<const LsqMeatImJob *>(d_meat), 4 * Kg, Dmax);
+    if (rc != NMRFIT_OK) return rc;
+    NMRFIT_HIP(hipMemcpyAsync(meat.M_out, d_M, (size_t)n_M * sizeof(double), hipMemcpyDeviceToHost, st));
+    return NMRFIT_OK;
+}
 
 // include/nmrfit_amd_lsq.h for the fits [k0, k1) of a part: their residual rows in ONE launch over the part's resident
 // spectra (lsq.hip, residual_rows_batch_kernel), J tile by tile and the segments' sums in a second, the ordered sums in
@@ -116,7 +158,9 @@ static int part_normal_group(BatchPart *b, int32_t k0, int32_t k1, size_t lds, u
     int rc = launch_rows_batch(st, d_fits, Kg, Smax, lds, aux_off, fit_im);
     if (rc != NMRFIT_OK) return rc;
     if (sums && (rc = launch_lsq(st, d_jobs, nch * Kg, Dmax, true)) != NMRFIT_OK) return rc;
-    if (meat && meat->M_out) {
+    if (meat && meat->M_out && fit_im) {
+        if ((rc = group_meat_im(b, k0, k1, jobs, rows, *meat, Dmax, mem)) != NMRFIT_OK) return rc;
+    } else if (meat && meat->M_out) {
         // the meat of every fit (real channel alone: job k - k0 is fit k's): R and c where the fit's LsqJob has them, the
         // fit's resident weights, the phase of its row 0; one more block of `mem`: [records | segments' sums | M]
         int64_t n_mpartial = 0;
@@ -189,10 +233,10 @@ static int part_normal_equations(BatchPart *b, const double *rows, const double 
     // groups of consecutive fits whose residual rows fit the workspace budget (a fit larger than the budget runs alone)
     int64_t budget = (int64_t)256 << 17;   // doubles: 256 MiB
     if (const char *e = getenv("NMRFIT_LSQ_WORKSPACE_MB")) budget = std::max<int64_t>(1, atoll(e)) << 17;
-    int64_t at_rows = 0, at_c = 0, at_A = 0;
+    int64_t at_rows = 0, at_c = 0, at_A = 0, at_M = 0;
     for (int32_t k0 = 0; k0 < b->K && rc == NMRFIT_OK;) {
         int32_t k1 = k0;
-        int64_t n_R = 0, d_rows = 0, d_c = 0, d_A = 0;
+        int64_t n_R = 0, d_rows = 0, d_c = 0, d_A = 0, d_M = 0;
         while (k1 < b->K) {
             const int64_t D = b->D[(size_t)k1], need = nch * (D + 1) * b->Nk[(size_t)k1];   // (both channels: the doubled rows)
             if (k1 > k0 && n_R + need > budget) break;
@@ -200,12 +244,13 @@ static int part_normal_equations(BatchPart *b, const double *rows, const double 
             d_rows += (D + 1) * D;
             d_c += D;
             d_A += nch * D * D;
+            d_M += meat_doubles(D, nch);
             ++k1;
         }
         {
             Scratch mem;
             const Meat group{meat ? meat->sigma_u + k0 : nullptr, meat ? meat->sigma_v + k0 : nullptr,
-                             meat && meat->M_out ? meat->M_out + at_A : nullptr};
+                             meat && meat->M_out ? meat->M_out + at_M : nullptr};
             rc = part_normal_group(b, k0, k1, lds, aux_off, rows + at_rows, c + at_c, s + k0, A_out ? A_out + at_A : nullptr,
                                    g_out ? g_out + nch * at_c : nullptr, f_out ? f_out + nch * k0 : nullptr, mem, fit_im,
                                    meat ? &group : nullptr);
@@ -214,6 +259,7 @@ static int part_normal_equations(BatchPart *b, const double *rows, const double 
         at_rows += d_rows;
         at_c += d_c;
         at_A += d_A;
+        at_M += d_M;
         k0 = k1;
     }
     return rc;
@@ -225,12 +271,12 @@ static int batch_normal_equations(nmrfit_batch *b, const char *who, int nch, con
                                   double *A_out, double *g_out, double *f_out, const Meat *meat = nullptr)
 {
     int rc = check_idle(b, who);
-    int64_t at_rows = 0, at_A = 0;
+    int64_t at_rows = 0, at_A = 0, at_M = 0;
     for (size_t p = 0; p < b->parts.size() && rc == NMRFIT_OK; ++p) {
         const int32_t f0 = b->first[p], f1 = b->first[p + 1];
         const int64_t at_c = b->boff[(size_t)f0];
         const Meat part{meat ? meat->sigma_u + f0 : nullptr, meat ? meat->sigma_v + f0 : nullptr,
-                        meat && meat->M_out ? meat->M_out + at_A : nullptr};
+                        meat && meat->M_out ? meat->M_out + at_M : nullptr};
         rc = part_normal_equations(b->parts[p], rows + at_rows, c + at_c, s + f0, A_out ? A_out + nch * at_A : nullptr,
                                    g_out ? g_out + nch * at_c : nullptr, f_out ? f_out + nch * f0 : nullptr,
                                    nch == 2 ? b->parts[p]->fit_im : 0, meat ? &part : nullptr);
@@ -238,6 +284,7 @@ static int batch_normal_equations(nmrfit_batch *b, const char *who, int nch, con
             const int64_t D = b->boff[(size_t)k + 1] - b->boff[(size_t)k];
             at_rows += (D + 1) * D;
             at_A += D * D;
+            at_M += meat_doubles(D, nch);
         }
     }
     return rc;
@@ -289,6 +336,27 @@ int nmrfit_batch_sandwich(nmrfit_batch *b, const double *rows, const double *c, 
     }
     const Meat meat{sigma_u, sigma_v, M_out};
     return batch_normal_equations(b, "nmrfit_batch_sandwich", 1, rows, c, s, A_out, g_out, f_out, &meat);
+}
+
+// include/nmrfit_amd_cov_im.h.  Every refusal comes before the first launch: the batch is as it was.
+int nmrfit_batch_sandwich_im(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
+                             const double *sigma_v, double *A_out, double *g_out, double *rho_out, double *M_out)
+{
+    int rc = check_batch_handle(b);
+    if (rc != NMRFIT_OK) return rc;
+    if (!rows || !c || !s || !sigma_u || !sigma_v)
+        return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich_im: null rows, c, s, sigma_u or sigma_v");
+    for (int32_t k = 0; k < b->K; ++k)
+        if ((rc = check_sigma("nmrfit_batch_sandwich_im", sigma_u[k], sigma_v[k])) != NMRFIT_OK) return rc;
+    for (const BatchPart *p : b->parts) {
+        if (p->fit_im != NMRFIT_FIT_IM_REFERENCE && p->fit_im != NMRFIT_FIT_IM_SUM)
+            return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich_im: the batch was created with fit_im = 0 (real part only): "
+                                            "nmrfit_batch_sandwich is the call for it");
+        if (4 + 3 * (int64_t)p->Pmax > kLsqMaxD)
+            return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich_im: D = 4 + 3 P <= " + std::to_string(kLsqMaxD) + " for every fit");
+    }
+    const Meat meat{sigma_u, sigma_v, M_out};
+    return batch_normal_equations(b, "nmrfit_batch_sandwich_im", 2, rows, c, s, A_out, g_out, rho_out, &meat);
 }
 
 }  // extern "C"

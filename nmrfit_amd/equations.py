@@ -231,6 +231,23 @@ class Evaluator:
         (``normal``) -- and ``f2`` [2] = (rho_re, rho_im) of row 0."""
         return self._jacobian("jacobian_im", True, fit_im, rows, c, s, J, r, normal)
 
+    def sandwich_im(self, rows, c, s, fit_im, sigma_u, sigma_v):
+        """``nmrfit_sandwich_im`` (include/nmrfit_amd_cov_im.h): a dict with ``A`` [2, D, D], ``g`` [2, D] and ``f2`` [2]
+        -- ``jacobian_im``'s bit for bit -- and ``M`` [3, D + 1, D + 1], the blocks (rr, ii, ri) of the two-channel meat
+        Mt_ab = Jt_a^T diag(q_ab) Jt_b with Jt_ch = [J_ch | r_ch], from the context's weights and the phase of row 0
+        under noise (sigma_u, sigma_v).  ``uncertainty.covariance_im`` makes standard errors of them.  DEFAULT kernel
+        variant, D <= 76."""
+        rows, P = self._as_batch(rows)
+        D = rows.shape[1]
+        c = _cabi.f64(c)
+        if rows.shape[0] != D + 1 or c.shape != (D,):
+            raise ValueError("sandwich_im: rows must be (D + 1) x D and c have D entries")
+        A, g, f2, M = np.empty((2, D, D)), np.empty((2, D)), np.empty(2), np.empty((3, D + 1, D + 1))
+        _cabi.check(self._lib.nmrfit_sandwich_im(self._ctx, P, fit_im_mode(fit_im), _cabi.ptr(rows), _cabi.ptr(c), float(s),
+                                                 float(sigma_u), float(sigma_v), _cabi.ptr(A), _cabi.ptr(g), _cabi.ptr(f2),
+                                                 _cabi.ptr(M)))
+        return dict(A=A, g=g, f2=f2, M=M)
+
     # -- device-resident helpers (bench / swarm) ------------------------------------------
     def dev_alloc(self, nbytes):
         p = ctypes.c_void_p()

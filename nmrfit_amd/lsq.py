@@ -161,13 +161,26 @@ class ResidualModel:
     def sandwich(self, x, sigma_u, sigma_v):
         """``(A, M, g, f)`` at x: ``normal_equations``'s A, g and f (the same launches, the same bits) and the meat
         M = J^T diag(q) J of the sandwich covariance under noise (sigma_u, sigma_v) on the two channels
-        (``Evaluator.sandwich``; ``uncertainty.covariance`` takes them).  Real channel only, D <= 76."""
+        (``Evaluator.sandwich``; ``uncertainty.covariance`` takes them).  Real channel only, D <= 76: a model made with a
+        ``fit_im`` mode has ``sandwich_im``."""
         if self.fit_im:
             raise ValueError("ResidualModel.sandwich: the covariance covers the real channel only (fit_im=False)")
         self.n_jac += 1
         rows, h = self.rows(x)
         out = self.ev.sandwich(rows, self._scale / h, self._scale, sigma_u, sigma_v)
         return out["A"], out["M"], out["g"], out["f"]
+
+    def sandwich_im(self, x, sigma_u, sigma_v):
+        """``(parts, meat)`` at x for a model made with a ``fit_im`` mode: ``parts`` the channels' ``(A_ch, g_ch, rho_ch)``
+        as ``combine_channels`` takes them -- the bits ``normal_equations`` combines -- and ``meat`` [3, D + 1, D + 1]
+        the blocks (rr, ii, ri) of the two-channel sandwich (``Evaluator.sandwich_im``); ``uncertainty.covariance_im``
+        takes both.  D <= 76."""
+        if not self.fit_im:
+            raise ValueError("ResidualModel.sandwich_im: the model was made without a fit_im mode: sandwich is its call")
+        self.n_jac += 1
+        rows, h = self.rows(x)
+        out = self.ev.sandwich_im(rows, self._scale / h, self._scale, self.fit_im, sigma_u, sigma_v)
+        return [(out["A"][ch], out["g"][ch], float(out["f2"][ch])) for ch in (0, 1)], out["M"]
 
     def objective(self, x):
         return float(np.linalg.norm(self.fun(x)))

@@ -19,7 +19,24 @@ Validity.  First order in the noise, Gauss-Newton: on a spectrum the model does 
 sum_j r_j grad^2 r_j of the Hessian is of relative size ~ noise x curvature (2e-3 of the standard errors on the noisy
 calibration case, tests/uncertainty_support.py).  The standard errors describe the noise alone: ``distance`` says how
 many of them the reported parameters lie from the local minimiser -- an unpolished swarm stops 0.06 ... 76 of them away
-(DESIGN.md 4.11).  Real channel only: a ``fit_im`` fit minimises a mean of two norms and is refused.
+(DESIGN.md 4.11).  Real channel only: a ``fit_im`` fit minimises a mean of two norms and is refused here -- its entrance
+is the two-channel sandwich below.
+
+Both channels (include/nmrfit_amd_cov_im.h, csrc/lsq_cov_im.hip).  A ``fit_im`` fit minimises
+f = (rho_re + rho_im)/2, rho_ch = ||r_ch||.  Its estimator solves grad f = sum_ch J_ch^T r_ch / (2 rho_ch) = 0, and with J
+held fixed the score moves with the data by
+
+    d(grad f) = 1/2 sum_ch (1/rho_ch) B_ch Jt_ch^T dr_ch,     Jt_ch = [J_ch | r_ch]  [N x (D + 1)],  B_ch = [I_D | -g_ch/rho_ch^2]
+    H   = 1/2 sum_ch (A_ch/rho_ch - g_ch g_ch^T/rho_ch^3)      the Gauss-Newton Hessian of f (not combine_channels' dominating H)
+    M   = 1/4 sum_a sum_b B_a Mt_ab B_b^T / (rho_a rho_b),     Mt_ab = Jt_a^T diag(q_ab) Jt_b
+    cov = H_ff^-1 M_ff H_ff^-1
+
+with q_rr = ws^2 (cos^2 phi sigma_u^2 + sin^2 phi sigma_v^2), q_ii = ws^2 (sin^2 phi sigma_u^2 + cos^2 phi sigma_v^2) and
+q_ri = ws^2 cos phi sin phi (sigma_u^2 - sigma_v^2), ws_j = weights_j s: V and I are two rotations of the same (u, v).  The
+device makes the three blocks Mt_rr, Mt_ii, Mt_ri next to A_ch, g_ch, rho_ch (``Evaluator.sandwich_im``,
+``lsq.ResidualModel.sandwich_im``, ``FitBatch.sandwich_im``); ``sandwich_host_im`` states them in numpy and
+``covariance_im`` does the algebra.  The errors belong to the minimiser of f: ``distance`` is measured with grad f, and
+``batch_polish="both"`` / ``FitBatch.polish(channels="both")`` is the polish that reaches that minimiser.
 """
 import numpy as np
 
@@ -52,6 +69,28 @@ def sandwich_host(J, weights, x, sigma_u, sigma_v):
     J = np.asarray(J, dtype=np.float64)
     q = residual_variance(weights, x, sigma_u, sigma_v)
     return (q[:, None] * J).T @ J
+
+
+def residual_covariances(weights, x, sigma_u, sigma_v):
+    """``(q_rr, q_ii, q_ri)`` [N each]: per grid point the variances of the weighted residuals of the real and the
+    imaginary channel and their covariance, with the phase of ``x``."""
+    weights = np.asarray(weights, dtype=np.float64)
+    N = weights.shape[0]
+    phi = float(x[0]) + float(x[1]) * (np.arange(N, dtype=np.float64) / N)
+    ws = weights * (1.0 / np.sqrt(N))
+    cs, sn = np.cos(phi), np.sin(phi)
+    var_u, var_v = sigma_u * sigma_u, sigma_v * sigma_v
+    return ((ws * ws) * (cs * cs * var_u + sn * sn * var_v), (ws * ws) * (sn * sn * var_u + cs * cs * var_v),
+            (ws * ws) * (cs * sn * (var_u - var_v)))
+
+
+def sandwich_host_im(J_re, r_re, J_im, r_im, weights, x, sigma_u, sigma_v):
+    """What csrc/lsq_cov_im.hip computes, in numpy: ``(Mt_rr, Mt_ii, Mt_ri)``, [(D + 1) x (D + 1)] each, with
+    Mt_ab = Jt_a^T diag(q_ab) Jt_b and Jt_ch = [J_ch | r_ch] -- the Jacobian [N x D] and the residual [N] of either
+    channel's weighted residual.  The device's blocks differ in summation order and in the last bits of sincos."""
+    Jt = [np.column_stack((np.asarray(J, dtype=np.float64), np.asarray(r, dtype=np.float64))) for J, r in ((J_re, r_re), (J_im, r_im))]
+    q_rr, q_ii, q_ri = residual_covariances(weights, x, sigma_u, sigma_v)
+    return (q_rr[:, None] * Jt[0]).T @ Jt[0], (q_ii[:, None] * Jt[1]).T @ Jt[1], (q_ri[:, None] * Jt[0]).T @ Jt[1]
 
 
 def area_fraction(x):
@@ -89,6 +128,14 @@ class FitUncertainty:
     sigma : (sigma_u, sigma_v) the record was made with, or None
     status : "ok" or "singular" (the Cholesky factorisation of the scaled A_ff failed, or nothing is free)
     x, A, M, g : what it was made from
+
+    A record made by ``covariance_im`` (a fit on both channels) has A = H, the Gauss-Newton Hessian of
+    f = (rho_re + rho_im)/2, M the meat of its score and g = grad f, and carries four attributes more -- a real-channel
+    record has none of them:
+    channels : "both"
+    rho : (rho_re, rho_im), NaN for an absent channel
+    parts : the channels' (A_ch, g_ch, rho_ch) it was made from, (re, im), None for an absent channel
+    meat : the blocks (Mt_rr, Mt_ii, Mt_ri) it was made from
     """
 
     def __init__(self, **kw):
@@ -156,18 +203,77 @@ def covariance(A, M, g, x, lower, upper, sigma=None):
                           status=status, x=x, A=A, M=M, g=g)
 
 
+def _channels(parts, meat):
+    """``covariance_im``'s arguments as two lists: [(A, g, rho) or None] for (re, im) and the 2 x 2 table of blocks."""
+    if isinstance(parts, dict):
+        parts = [parts.get("re"), parts.get("im")]
+    parts = list(parts)
+    if isinstance(meat, dict):
+        meat = [meat.get("rr"), meat.get("ii"), meat.get("ri")]
+    rr, ii, ri = (None if m is None else np.asarray(m, dtype=np.float64) for m in meat)
+    return parts, [[rr, ri], [None if ri is None else ri.T, ii]]
+
+
+def covariance_im(parts, meat, x, lower, upper, sigma=None):
+    """The ``FitUncertainty`` of one fit made on both channels, from its pieces: ``parts`` the channels' normal equations
+    (a dict with "re" and / or "im", or the pair (re, im) with None for an absent channel, of ``(A_ch, g_ch, rho_ch)`` as
+    ``lsq.combine_channels`` takes them) and ``meat`` the blocks ``(Mt_rr, Mt_ii, Mt_ri)`` (or a dict with "rr", "ii",
+    "ri"; the blocks of an absent channel may be None) at the parameters ``x`` inside the box.
+
+    H, M and the gradient of f = (rho_re + rho_im)/2 are formed as the module's docstring states them; a channel whose rho
+    is 0 or not finite contributes nothing to any of them, as in ``combine_channels``.  Fixed parameters, the scaling,
+    the Cholesky factorisation and the record are ``covariance``'s: H is not guaranteed positive definite, and a failed
+    factorisation gives NaN and ``status == "singular"``, never an exception.  The record carries ``A`` = H, ``M`` = M,
+    ``g`` = grad f, ``rho`` = (rho_re, rho_im) (NaN for an absent channel), ``channels`` = "both", and the pieces it
+    was made from as ``parts`` and ``meat``.  ``newton_step`` is -H_ff^-1 grad f_f: the errors and ``distance`` belong to
+    the minimiser of f.  Plain numpy."""
+    x = np.asarray(x, dtype=np.float64)
+    D = x.shape[0]
+    parts, blocks = _channels(parts, meat)
+    H, M, grad = np.zeros((D, D)), np.zeros((D, D)), np.zeros(D)
+    rho, B = [float("nan")] * 2, [None] * 2
+    for ch, part in enumerate(parts):
+        if part is None:
+            continue
+        A, g, r = np.asarray(part[0], dtype=np.float64), np.asarray(part[1], dtype=np.float64), float(part[2])
+        rho[ch] = r
+        if not (np.isfinite(r) and r > 0.0):
+            continue
+        H += 0.5 * (A / r - np.outer(g, g) / (r * r * r))
+        grad += g * (0.5 / r)
+        B[ch] = np.column_stack((np.eye(D), -g / (r * r))) / r        # B_ch / rho_ch
+    for a in (0, 1):
+        for b in (0, 1):
+            if B[a] is not None and B[b] is not None:
+                if blocks[a][b] is None:
+                    raise ValueError("covariance_im: the meat lacks the block of channels (%d, %d)" % (a, b))
+                M += 0.25 * (B[a] @ blocks[a][b] @ B[b].T)
+    M = 0.5 * (M + M.T)
+    fu = covariance(H, M, grad, x, lower, upper, sigma=sigma)
+    fu.rho, fu.channels, fu.parts, fu.meat = tuple(rho), "both", parts, meat
+    return fu
+
+
 def option(uncertainty):
     """``fit_many``'s ``uncertainty=`` as its record keeps it: None, or a dict with ``sigma`` (a float or a pair) or
-    ``noise_region=(xstart, xstop)`` -- neither: every job must bring its own -- and ``device_sigma`` (bool)."""
+    ``noise_region=(xstart, xstop)`` -- neither: every job must bring its own -- and ``device_sigma`` (bool).
+    ``channels="both"`` (the default "real" leaves the dict as it always was): the ``fit_im`` jobs of the call get the
+    two-channel record (``covariance_im``) instead of being refused."""
     if uncertainty is None or uncertainty is False:
         return None
     if not isinstance(uncertainty, dict):
         raise ValueError("fit_many: uncertainty is a dict with sigma (a float or a pair) or noise_region=(xstart, xstop)")
-    unknown = set(uncertainty) - {"sigma", "noise_region", "device_sigma"}
+    unknown = set(uncertainty) - {"sigma", "noise_region", "device_sigma", "channels"}
     if unknown:
         raise ValueError("fit_many: uncertainty has no option %s" % ", ".join(sorted(map(repr, unknown))))
-    return dict(sigma=uncertainty.get("sigma"), noise_region=uncertainty.get("noise_region"),
-                device_sigma=bool(uncertainty.get("device_sigma", False)))
+    channels = uncertainty.get("channels", "real")
+    if not isinstance(channels, str) or channels not in ("real", "both"):
+        raise ValueError('fit_many: uncertainty channels is "real" or "both", got %r' % (channels,))
+    out = dict(sigma=uncertainty.get("sigma"), noise_region=uncertainty.get("noise_region"),
+               device_sigma=bool(uncertainty.get("device_sigma", False)))
+    if channels == "both":
+        out["channels"] = "both"
+    return out
 
 
 def job_sigmas(jobs, opts, device=0):

@@ -472,25 +472,36 @@ class FitUtility:
                                               device=self._device())
         return self.quality
 
-    def uncertainty(self, sigma=None, noise_region=None):
+    def uncertainty(self, sigma=None, noise_region=None, channels="real"):
         """The ``uncertainty.FitUncertainty`` of this finished fit at ``params``: first-order standard errors of the
         parameters and of the satellite area fraction from ONE launch of the D + 1 residual rows on a context
         (nmrfit_sandwich, csrc/lsq_cov.hip) -- the sandwich A^-1 M A^-1, not sigma^2 (J^T J)^-1 / N: the weights are not
         1/sigma -- and ``distance``, how many of them ``params`` lies from the local minimiser (large after an unpolished
         swarm).  ``sigma``: the noise of the spectrum, a float or a pair (sigma_u, sigma_v); else
         ``noise_region=(xstart, xstop)``, a signal-free stretch -- as ``fit_replicas`` takes them.  Real channel only
-        (``fit_im=False``), at most 24 peaks.  The record is returned, not kept: on the fits that
+        (``fit_im=False``) unless ``channels="both"``: a ``fit_im`` fit then gets the two-channel record
+        (nmrfit_sandwich_im, ``uncertainty.covariance_im``), whose errors belong to the minimiser of
+        f = (rho_re + rho_im)/2 -- ``distance`` is measured with grad f, and a polish on both channels
+        (``batch_polish="both"``) is what reaches that minimiser; a ``fit_im=False`` fit gets the same record either way.
+        At most 24 peaks.  The record is returned, not kept: on the fits that
         ``fit_many(uncertainty=...)`` returns, the attribute ``uncertainty`` IS their record (it stands in this method's
         place there)."""
         from . import lsq, noise, uncertainty
         if 'params' not in self.__dict__:      # (not hasattr: __getattr__ answers for missing names)
             raise AttributeError("uncertainty: this fit has no params yet (call fit() first)")
-        if equations.fit_im_mode(self.fit_im):
-            raise ValueError("uncertainty: the covariance covers the real channel only (fit_im=False)")
+        if channels not in ("real", "both"):
+            raise ValueError('uncertainty: channels is "real" or "both"')
+        mode = equations.fit_im_mode(self.fit_im)
+        if mode and channels != "both":
+            raise ValueError("uncertainty: the covariance covers the real channel only (fit_im=False); "
+                             'channels="both" is the entrance of a fit_im fit')
         su, sv = noise._job_sigma(dict(sigma=sigma, noise_region=noise_region), self.data)
         lower, upper = _cabi.f64(self.lower), _cabi.f64(self.upper)
         ev = equations.Evaluator(self.data.w, self.data.u, self.data.v, self.weights, device=self._device())
         try:
+            if mode:
+                parts, meat = lsq.ResidualModel(ev, lower, upper, fit_im=mode).sandwich_im(self.params, su, sv)
+                return uncertainty.covariance_im(parts, meat, self.params, lower, upper, sigma=(su, sv))
             A, M, g, _ = lsq.ResidualModel(ev, lower, upper).sandwich(self.params, su, sv)
         finally:
             ev.close()
