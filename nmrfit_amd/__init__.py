@@ -27,6 +27,10 @@ around it, behind the reference's own API for that path:
     nmrfit_amd.fit_many(jobs, fit_im="sum", batch_polish="both", uncertainty=dict(sigma=s, channels="both"))
                                                                  the same for fit_im fits: the two-channel sandwich
 
+    nmrfit_amd.spectra_from_fids(fids, sw, sfrq, tof, zero_fill="pow2")   raw FIDs to Data on the DEVICE: a batched fp64 Fourier
+                                                                 transform, core.load's centring, reversal, normalisation and
+                                                                 trace sum (fid.transform_many alone; the file readers stay out)
+
 Everything that evaluates the objective goes through libnmrfit_amd.so (include/nmrfit_amd.h);
 there is no CPU fallback.  The automatic phase estimate and the automatic peak picking run on the device too when
 asked for by shift_phase_many / proc_autophase.approximate_phase_many and select_peaks_many / peaks.find_peaks_many
@@ -37,11 +41,12 @@ bounds are host code.  Instrument I/O (nmrfit.load), the
 matplotlib click selectors and plotting are out of scope.
 """
 from .core import fit, fit_many  # noqa: F401
-from . import baseline, batch, containers, equations, noise, peaks, proc_autophase, pso, quality, synth, uncertainty, utils  # noqa: F401
+from . import baseline, batch, containers, equations, fid, noise, peaks, proc_autophase, pso, quality, synth, uncertainty, utils  # noqa: F401
 from .uncertainty import FitUncertainty  # noqa: F401
 from .quality import FitQuality, residual_stats, residual_stats_many  # noqa: F401
 from .noise import fit_replicas, fit_replicas_many  # noqa: F401
 from .containers import Data, correct_baseline_many, select_peaks_many, shift_phase_many  # noqa: F401
 from .baseline import BaselineFit, sample_noise_many, subtract_rotated  # noqa: F401
+from .fid import spectra_from_fids  # noqa: F401
 
 __version__ = "0.1.0"

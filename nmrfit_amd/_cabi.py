@@ -201,6 +201,11 @@ COV_IM_SIGNATURES = {
     "nmrfit_sandwich_im": [_VP, _I32, _INT, _VP, _VP, _F64, _F64, _F64, _VP, _VP, _VP, _VP],
     "nmrfit_batch_sandwich_im": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# FID_SIGNATURES: include/nmrfit_amd_fid.h (raw FIDs to spectra: a batched fp64 Fourier transform with zero filling, the
+# loader's centring, reversal, normalisation and sum over traces)
+FID_SIGNATURES = {
+    "nmrfit_fid_transform": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                 # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -305,7 +310,8 @@ def lib():
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
                 + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
-                + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()):
+                + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()) \
+                + list(FID_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -1,0 +1,533 @@
+// fid.hip -- raw FIDs to spectra on the GPU (opt-in; include/nmrfit_amd_fid.h holds the definition): a batched fp64
+// complex Fourier transform with zero filling, the centring and reversal of the reference's loader in the last pass's
+// store, then the normaliser (a lexicographic maximum), the quotient by Smith's rule and the sum over traces.
+//   fid_short_kernel      a workgroup of 256 threads per trace of n <= 4096 points: load with zero fill, every stage in
+//                         LDS, the centred and reversed store
+//   fid_pass1_kernel      n = n1 n2 > 4096: a workgroup takes 4096 / n1 adjacent columns (stride n2) of one trace,
+//                         transforms them in LDS and stores them times the twiddle omega_n^(j2 q1)
+//   fid_pass2_kernel      ... and 4096 / n2 adjacent rows (n2 contiguous points each), whose store centres and reverses
+//   fid_max_part_kernel   the lexicographic maximum and a not-finite flag of 8192 values of a spectrum
+//   fid_max_kernel        ... of the partial maxima of a spectrum: the row
+//   fid_finish_kernel     1024 output points of a spectrum: the quotient of every trace's value, summed over the traces
+// Every launch is a flat list of work items over all spectra of the call; a workgroup finds its spectrum by a binary
+// search in the launch's prefix table (K + 1 numbers): at most six launches whatever K and T.  No atomics, no scratch
+// memory; every value is a pure function of the spectrum's own input (the definition's PURITY).
+//
+// THE LDS BLOCK.  Up to 4096 complex points as two planes of doubles (re, im).  C = 2^lgC transforms of length L are
+// interleaved, point p of transform c at index p C + c, so a stage of C > 1 transforms is a stage of one transform of
+// C L points that stops early.  A stage of radix R reads its R inputs at b + r M / R (b: the butterfly, M = C L):
+// consecutive lanes read consecutive doubles.  It writes runs of Ns C consecutive doubles R Ns C apart (Ns: the length
+// already transformed), and the row loads of pass 2 write R doubles apart: power-of-two strides, which unswizzled land
+// 2 to 16 lanes of a 16-lane store group (16 eight-byte slots of the 32 banks a ds_write sees) on one slot.  swz()
+// XORs the low four bits of an index with a GF(2)-linear function of bits 4 .. 8 that makes every one of these
+// patterns -- runs of 1, 2, 4, 8 at radix 2 or 4, strides 2 .. 32, and unit stride -- a bijection of the 16 lanes onto
+// the 16 slots, and leaves 32 consecutive aligned doubles on 32 distinct slots of the 64 banks a ds_read_b64 sees
+// (tests/test_fid_cpu.py enumerates the patterns).  The XOR stays inside an aligned block of 16: no padding, 64 KiB for
+// 4096 points, two workgroups per CU.
+//
+// A stage is in place: every thread reads the inputs of its butterflies into registers, the workgroup meets, every
+// thread writes.  Radix 4 keeps 4 butterflies x 4 points (64 VGPRs of data) per thread at 4096 points and halves the
+// stages, and with them the barriers and the LDS traffic, against radix 2; an odd log2 L takes ONE radix-2 stage first
+// (its twiddles are all 1).
+#include "fid_twiddle.h"
+#include "host_call.h"
+#include "nmrfit_amd_fid.h"
+#include "weights_internal.h"
+
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace nmrfit {
+namespace {
+
+#pragma clang fp contract(off)   // (every product and sum of the definition is rounded once)
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kRow = NMRFIT_FID_ROW;
+constexpr int kLgLds = NMRFIT_FID_LDS_LOG2, kLdsPoints = 1 << kLgLds;
+constexpr int kLgMax = NMRFIT_FID_MAX_LOG2;
+constexpr int kMaxChunk = 8192;      // values per partial maximum
+constexpr int kFinishChunk = 1024;   // output points per finishing workgroup
+constexpr unsigned kGridX = 32768;   // work items per grid row (an item is blockIdx.y * gridDim.x + blockIdx.x)
+static_assert(kLgLds == kFidLgStage && kLgMax == kFidLgMax, "the twiddle tables are sized for these lengths");
+static_assert(kLgMax <= 2 * (kLgLds - 1), "both factors of a long transform leave at least two transforms per block");
+
+// One spectrum of a call.  Every pointer is device memory.
+struct FidJob {
+    const double2 *x;    // T traces of n_in points
+    double2 *work;       // T traces of n points between the passes (n > 4096)
+    double2 *z;          // T traces of n points: Y in the output order
+    double *u, *v;       // n points each
+    double *row;         // [kRow]
+    double4 *part;       // the partial maxima: (re, im, flat index, not-finite flag)
+    int32_t n_in, n, T, lg, lg1, lg2, parts;
+};
+
+struct Cx {
+    double re, im;
+};
+__device__ __forceinline__ Cx cmul(Cx a, Cx w) { return Cx{a.re * w.re - a.im * w.im, a.re * w.im + a.im * w.re}; }
+__device__ __forceinline__ Cx cadd(Cx a, Cx b) { return Cx{a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ Cx csub(Cx a, Cx b) { return Cx{a.re - b.re, a.im - b.im}; }
+
+// where index a of the block lies in a plane (the header comment: THE LDS BLOCK)
+__device__ __forceinline__ int swz(int a)
+{
+    const int h = a >> 4;
+    return a ^ ((-(h & 1) & 15) ^ (-((h >> 1) & 1) & 10) ^ ((h >> 2) & 7));
+}
+
+// the work item of this workgroup, or -1 past the end (the whole workgroup leaves)
+__device__ __forceinline__ long long work_item(long long total)
+{
+    const long long item = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+    return item < total ? item : -1;
+}
+
+// the spectrum of an item: the largest k < K with pref[k] <= item (a spectrum without items has pref[k] == pref[k + 1])
+__device__ __forceinline__ int find_job(const long long *__restrict__ pref, int K, long long item)
+{
+    int lo = 0, hi = K;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pref[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One in-place stage of radix R on M = C L points: Ns = 2^lgNs points of every transform are transformed already.
+template <int R>
+__device__ __forceinline__ void lds_stage(double *__restrict__ re, double *__restrict__ im, int M, int lgC, int lgNs,
+                                          const FidTw *__restrict__ tw)
+{
+    constexpr int kPer = kLdsPoints / R / kThreads;   // butterflies per thread at a full block
+    constexpr int lgR = R == 4 ? 2 : 1;
+    const int nb = M >> lgR;
+    Cx x[kPer][R];
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) {
+        const int b = (int)threadIdx.x + i * kThreads;
+        if (b < nb) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int at = swz(b + r * nb);
+                x[i][r] = Cx{re[at], im[at]};
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) {
+        const int b = (int)threadIdx.x + i * kThreads;
+        if (b < nb) {
+            const int j = b >> lgC, c = b & ((1 << lgC) - 1);
+            const int k = j & ((1 << lgNs) - 1);
+            const int out = ((((j - k) << lgR) + k) << lgC) + c, step = 1 << (lgNs + lgC);
+            Cx y[R];
+            if constexpr (R == 2) {   // (the first stage of an odd log2 L: Ns = 1, every twiddle is 1)
+                y[0] = cadd(x[i][0], x[i][1]);
+                y[1] = csub(x[i][0], x[i][1]);
+            } else {
+                const int ts = kFidLgStage - 2 - lgNs;   // omega_{4 Ns}^(k r) = omega_4096^(k r 4096 / (4 Ns))
+                const FidTw w1 = tw[k << ts], w2 = tw[(2 * k) << ts], w3 = tw[(3 * k) << ts];
+                const Cx z1 = cmul(x[i][1], Cx{w1.re, w1.im}), z2 = cmul(x[i][2], Cx{w2.re, w2.im});
+                const Cx z3 = cmul(x[i][3], Cx{w3.re, w3.im});
+                const Cx s02 = cadd(x[i][0], z2), d02 = csub(x[i][0], z2), s13 = cadd(z1, z3), d13 = csub(z1, z3);
+                const Cx mi = Cx{d13.im, -d13.re};   // -i d13
+                y[0] = cadd(s02, s13);
+                y[1] = cadd(d02, mi);
+                y[2] = csub(s02, s13);
+                y[3] = csub(d02, mi);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int at = swz(out + r * step);
+                re[at] = y[r].re;
+                im[at] = y[r].im;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// C = 2^lgC interleaved transforms of length 2^lgL in the block, M = C L points.  The caller's loads are followed by a
+// barrier; the last stage ends with one.  Every thread of the workgroup makes the same number of stages.
+__device__ __forceinline__ void lds_fft(double *__restrict__ re, double *__restrict__ im, int M, int lgC, int lgL,
+                                        const FidTw *__restrict__ tw)
+{
+    int lgNs = 0;
+    if (lgL & 1) {
+        lds_stage<2>(re, im, M, lgC, 0, tw);
+        lgNs = 1;
+    }
+    for (; lgNs < lgL; lgNs += 2) lds_stage<4>(re, im, M, lgC, lgNs, tw);
+}
+
+__global__ __launch_bounds__(kThreads) void fid_short_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
+                                                             int K, int plane, const FidTw *__restrict__ tw)
+{
+    extern __shared__ __align__(16) double lds[];
+    double *re = lds, *im = lds + plane;
+    const long long item = work_item(pref[K]);
+    if (item < 0) return;
+    const int k = find_job(pref, K, item);
+    const FidJob &q = jobs[k];
+    const long long t = item - pref[k];
+    const int n = q.n, n_in = q.n_in;
+    const double2 *__restrict__ x = q.x + t * n_in;
+    for (int e = threadIdx.x; e < n; e += kThreads) {
+        const double2 val = e < n_in ? x[e] : make_double2(0.0, 0.0);
+        const int at = swz(e);
+        re[at] = val.x;
+        im[at] = val.y;
+    }
+    __syncthreads();
+    lds_fft(re, im, n, 0, q.lg, tw);
+    double2 *__restrict__ z = q.z + t * n;
+    for (int j = threadIdx.x; j < n; j += kThreads) {
+        const int at = swz((n - 1 - j) ^ (n >> 1));   // Z[j] = Y[n - 1 - j] = X[(n - 1 - j + n / 2) mod n]
+        z[j] = make_double2(re[at], im[at]);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void fid_pass1_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
+                                                             int K, const FidTw *__restrict__ tw, const FidTwDD *__restrict__ hi,
+                                                             const FidTwDD *__restrict__ lo)
+{
+    extern __shared__ __align__(16) double lds[];
+    double *re = lds, *im = lds + kLdsPoints;
+    const long long item = work_item(pref[K]);
+    if (item < 0) return;
+    const int k = find_job(pref, K, item);
+    const FidJob &q = jobs[k];
+    const long long local = item - pref[k];
+    const int lg1 = q.lg1, lg2 = q.lg2, lgC = kLgLds - lg1, n2 = 1 << lg2, n_in = q.n_in;
+    const long long t = local >> (lg2 - lgC);                        // n2 / C groups of columns per trace
+    const int col0 = (int)(local & ((1 << (lg2 - lgC)) - 1)) << lgC;   // the group's first column
+    const double2 *__restrict__ x = q.x + t * n_in;
+    for (int e = threadIdx.x; e < kLdsPoints; e += kThreads) {
+        const int c = e & ((1 << lgC) - 1), j1 = e >> lgC;
+        const int s = (j1 << lg2) + col0 + c;
+        const double2 val = s < n_in ? x[s] : make_double2(0.0, 0.0);
+        const int at = swz(e);
+        re[at] = val.x;
+        im[at] = val.y;
+    }
+    __syncthreads();
+    lds_fft(re, im, kLdsPoints, lgC, lg1, tw);
+    double2 *__restrict__ work = q.work + t * q.n;
+    const int up = kLgMax - q.lg;   // omega_n^(j2 q1) = omega_{2^22}^(j2 q1 2^22 / n)
+    for (int e = threadIdx.x; e < kLdsPoints; e += kThreads) {
+        const int c = e & ((1 << lgC) - 1), q1 = e >> lgC, j2 = col0 + c;
+        const FidTw w = fid_split_twiddle(hi, lo, (j2 * q1) << up);
+        const int at = swz(e);
+        const Cx val = cmul(Cx{re[at], im[at]}, Cx{w.re, w.im});
+        work[(q1 << lg2) + j2] = make_double2(val.re, val.im);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void fid_pass2_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
+                                                             int K, const FidTw *__restrict__ tw)
+{
+    extern __shared__ __align__(16) double lds[];
+    double *re = lds, *im = lds + kLdsPoints;
+    const long long item = work_item(pref[K]);
+    if (item < 0) return;
+    const int k = find_job(pref, K, item);
+    const FidJob &q = jobs[k];
+    const long long local = item - pref[k];
+    const int lg1 = q.lg1, lg2 = q.lg2, lgR = kLgLds - lg2, n = q.n;
+    const long long t = local >> (lg1 - lgR);                        // n1 / R groups of rows per trace
+    const int row0 = (int)(local & ((1 << (lg1 - lgR)) - 1)) << lgR;   // the group's first row
+    const double2 *__restrict__ work = q.work + t * n + ((long long)row0 << lg2);   // R rows: 4096 contiguous points
+    for (int e = threadIdx.x; e < kLdsPoints; e += kThreads) {
+        const int r = e >> lg2, j2 = e & ((1 << lg2) - 1);
+        const double2 val = work[e];
+        const int at = swz((j2 << lgR) + r);
+        re[at] = val.x;
+        im[at] = val.y;
+    }
+    __syncthreads();
+    lds_fft(re, im, kLdsPoints, lgR, lg2, tw);
+    double2 *__restrict__ z = q.z + t * n;
+    for (int e = threadIdx.x; e < kLdsPoints; e += kThreads) {
+        const int r = e & ((1 << lgR) - 1), q2 = e >> lgR;
+        const int xq = row0 + r + (q2 << lg1);   // X's index q = q1 + n1 q2
+        const int at = swz(e);
+        z[n - 1 - (xq ^ (n >> 1))] = make_double2(re[at], im[at]);
+    }
+}
+
+// the running lexicographic maximum: (re, im, the flat index in Y's order); `bad`: a value that is not finite was seen
+struct Best {
+    double re, im;
+    long long idx;
+    int bad;
+};
+__device__ __forceinline__ Best best_init() { return Best{-INFINITY, -INFINITY, LLONG_MAX, 0}; }
+__device__ __forceinline__ void best_take(Best &a, double re, double im, long long idx, int bad)
+{
+    const bool better = re > a.re || (re == a.re && (im > a.im || (im == a.im && idx < a.idx)));
+    if (better) {
+        a.re = re;
+        a.im = im;
+        a.idx = idx;
+    }
+    a.bad |= bad;
+}
+
+// the workgroup's maximum in thread 0 (maxima are exact: the order of the reduction is free)
+__device__ __forceinline__ Best best_of_workgroup(Best mine, Best *s_best)
+{
+    for (int o = kWave / 2; o > 0; o >>= 1)
+        best_take(mine, __shfl_xor(mine.re, o), __shfl_xor(mine.im, o), __shfl_xor(mine.idx, o), __shfl_xor(mine.bad, o));
+    if (threadIdx.x % kWave == 0) s_best[threadIdx.x / kWave] = mine;
+    __syncthreads();
+    Best all = s_best[0];
+    for (int wv = 1; wv < kWaves; ++wv) best_take(all, s_best[wv].re, s_best[wv].im, s_best[wv].idx, s_best[wv].bad);
+    return all;
+}
+
+__global__ __launch_bounds__(kThreads) void fid_max_part_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
+                                                                int K)
+{
+    __shared__ Best s_best[kWaves];
+    const long long item = work_item(pref[K]);
+    if (item < 0) return;
+    const int k = find_job(pref, K, item);
+    const FidJob &q = jobs[k];
+    const int chunk = (int)(item - pref[k]), n = q.n;
+    const long long total = (long long)q.T * n, from = (long long)chunk * kMaxChunk;
+    const long long to = from + kMaxChunk < total ? from + kMaxChunk : total;
+    const double2 *__restrict__ z = q.z;
+    Best mine = best_init();
+    for (long long p = from + threadIdx.x; p < to; p += kThreads) {
+        const double2 val = z[p];
+        const long long j = p & (n - 1);
+        // (Z[t n + j] is Y[t n + n - 1 - j])
+        best_take(mine, val.x, val.y, p + (n - 1) - 2 * j, !(isfinite(val.x) && isfinite(val.y)));
+    }
+    const Best all = best_of_workgroup(mine, s_best);
+    if (threadIdx.x == 0) q.part[chunk] = make_double4(all.re, all.im, all.bad ? 0.0 : (double)all.idx, all.bad ? 1.0 : 0.0);
+}
+
+__global__ __launch_bounds__(kThreads) void fid_max_kernel(const FidJob *__restrict__ jobs)
+{
+    __shared__ Best s_best[kWaves];
+    const FidJob &q = jobs[blockIdx.x];
+    Best mine = best_init();
+    for (int p = threadIdx.x; p < q.parts; p += kThreads) {
+        const double4 part = q.part[p];
+        best_take(mine, part.x, part.y, (long long)part.z, part.w != 0.0);
+    }
+    const Best all = best_of_workgroup(mine, s_best);
+    if (threadIdx.x == 0) {
+        const double nan = __builtin_nan("");
+        double *row = q.row;
+        row[0] = all.bad ? 2.0 : (all.re == 0.0 && all.im == 0.0 ? 1.0 : 0.0);
+        row[1] = all.bad ? nan : all.re;
+        row[2] = all.bad ? nan : all.im;
+        row[3] = all.bad ? nan : (double)all.idx;
+        row[4] = (double)q.n;
+        row[5] = (double)q.T;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void fid_finish_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
+                                                              int K)
+{
+    const long long item = work_item(pref[K]);
+    if (item < 0) return;
+    const int k = find_job(pref, K, item);
+    const FidJob &q = jobs[k];
+    const int n = q.n, T = q.T, from = (int)(item - pref[k]) * kFinishChunk;
+    const double status = q.row[0], mr = q.row[1], mi = q.row[2];
+    const bool first = fabs(mr) >= fabs(mi);
+    const double rat = first ? mi / mr : mr / mi;
+    const double scl = first ? 1.0 / (mr + mi * rat) : 1.0 / (mi + mr * rat);
+    const double2 *__restrict__ z = q.z;
+    for (int j = from + (int)threadIdx.x; j < n && j < from + kFinishChunk; j += kThreads) {
+        double u = 0.0, v = 0.0;   // (np.sum's start: a sum of -0.0 alone comes out as +0.0)
+        for (int t = 0; t < T; ++t) {
+            const double2 val = z[(long long)t * n + j];
+            const double a = val.x, b = val.y;
+            const double qr = first ? (a + b * rat) * scl : (a * rat + b) * scl;
+            const double qi = first ? (b - a * rat) * scl : (b * rat - a) * scl;
+            u = u + qr;
+            v = v + qi;
+        }
+        if (status != 0.0) u = v = __builtin_nan("");
+        q.u[j] = u;
+        q.v[j] = v;
+    }
+}
+
+// the twiddle tables, made once per process on the host (fid_twiddle.h)
+struct FidTables {
+    std::vector<FidTw> stage;
+    std::vector<FidTwDD> hi, lo;
+    FidTables() : stage(kFidStage), hi(kFidSplit), lo(kFidSplit)
+    {
+        fid_fill_stage_table(stage.data());
+        fid_fill_split_tables(hi.data(), lo.data());
+    }
+};
+const FidTables &fid_tables()
+{
+    static const FidTables t;
+    return t;
+}
+
+dim3 item_grid(long long items)
+{
+    const unsigned gx = (unsigned)std::min<long long>(items, kGridX);
+    return dim3(gx, (unsigned)((items + gx - 1) / gx));
+}
+
+int log2_exact(int64_t n)   // -1 unless n is a power of two
+{
+    if (n <= 0 || (n & (n - 1))) return -1;
+    int lg = 0;
+    while (((int64_t)1 << lg) < n) ++lg;
+    return lg;
+}
+
+}  // namespace
+}  // namespace nmrfit
+
+using namespace nmrfit;
+
+#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
+
+int nmrfit_fid_transform(int device, int32_t K, const int64_t *n_in, const int64_t *n, const int32_t *T, const double *fid,
+                         double *u_out, double *v_out, double *rows_out, double *transform_out)
+{
+    const std::string who = "nmrfit_fid_transform";
+    if (K <= 0 || !n_in || !n || !T || !fid || !u_out || !v_out || !rows_out)
+        return refuse(NMRFIT_E_INVALID, who + ": the number of spectra must be > 0 and n_in, n, T, fid, u_out, v_out, rows_out non-null");
+    for (int32_t k = 0; k < K; ++k) {
+        if (T[k] <= 0 || n_in[k] <= 0)
+            return refuse(NMRFIT_E_INVALID, who + ": every spectrum needs T > 0 and n_in > 0 (spectrum " + std::to_string(k) + ")");
+        if (n[k] < n_in[k])
+            return refuse(NMRFIT_E_INVALID, who + ": a transform length is at least the trace's length (spectrum " + std::to_string(k) + ")");
+    }
+    const int64_t max_values = (int64_t)1 << 26;
+    int64_t values = 0, points = 0, in_values = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        const int lg = log2_exact(n[k]);
+        if (lg < 1 || lg > kLgMax)
+            return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
+                                                    " (spectrum " + std::to_string(k) + "): zero fill to the next power of two");
+        if (values <= max_values) {   // (each term < 2^53: the sums cannot overflow)
+            values += (int64_t)T[k] * n[k];
+            in_values += (int64_t)T[k] * n_in[k];
+        }
+        points += n[k];
+    }
+    if (K > kWeightsMaxSpectra || values > max_values)
+        return refuse(NMRFIT_E_UNSUPPORTED, who + ": a call takes at most " + std::to_string(kWeightsMaxSpectra) + " spectra and " +
+                                                std::to_string(max_values) + " transformed values (T n summed over the spectra)");
+    int rc = use_device(device);
+    if (rc != NMRFIT_OK) return rc;
+    StreamLease lease(device);
+    NMRFIT_HIP(lease.take());
+    hipStream_t st = lease.s;
+
+    // the work items of every launch: prefix tables over the spectra
+    const size_t nk = (size_t)K;
+    std::vector<long long> pref(5 * (nk + 1), 0);
+    long long *p_short = pref.data(), *p_one = p_short + nk + 1, *p_two = p_one + nk + 1, *p_max = p_two + nk + 1,
+              *p_fin = p_max + nk + 1;
+    int64_t work_values = 0;
+    int max_short = 0;
+    for (size_t k = 0; k < nk; ++k) {
+        const int lg = log2_exact(n[k]);
+        const bool is_short = lg <= kLgLds;
+        const int lg1 = lg / 2, lg2 = lg - lg1;
+        const long long Tk = T[k], total = Tk * n[k];
+        p_short[k + 1] = p_short[k] + (is_short ? Tk : 0);
+        p_one[k + 1] = p_one[k] + (is_short ? 0 : Tk << (lg2 - (kLgLds - lg1)));
+        p_two[k + 1] = p_two[k] + (is_short ? 0 : Tk << (lg1 - (kLgLds - lg2)));
+        p_max[k + 1] = p_max[k] + (total + kMaxChunk - 1) / kMaxChunk;
+        p_fin[k + 1] = p_fin[k] + (n[k] + kFinishChunk - 1) / kFinishChunk;
+        if (is_short) max_short = std::max(max_short, (int)n[k]);
+        else work_values += total;
+    }
+    const FidTables &tables = fid_tables();
+    Scratch mem;   // one allocation for the call's buffers
+    Carver c;
+    const size_t o_jobs = c.take(nk * sizeof(FidJob)), o_pref = c.take(pref.size() * sizeof(long long));
+    const size_t o_tw = c.take(kFidStage * sizeof(FidTw)), o_hi = c.take(kFidSplit * sizeof(FidTwDD)),
+                 o_lo = c.take(kFidSplit * sizeof(FidTwDD));
+    const size_t o_x = c.take((size_t)in_values * sizeof(double2)), o_work = c.take((size_t)work_values * sizeof(double2));
+    const size_t o_z = c.take((size_t)values * sizeof(double2)), o_u = c.take((size_t)points * sizeof(double)),
+                 o_v = c.take((size_t)points * sizeof(double));
+    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)p_max[nk] * sizeof(double4));
+    unsigned char *base = nullptr;
+    NMRFIT_HIP(mem.alloc(&base, c.total));
+    FidJob *d_jobs = reinterpret_cast<FidJob *>(base + o_jobs);
+    long long *d_pref = reinterpret_cast<long long *>(base + o_pref);
+    FidTw *d_tw = reinterpret_cast<FidTw *>(base + o_tw);
+    FidTwDD *d_hi = reinterpret_cast<FidTwDD *>(base + o_hi), *d_lo = reinterpret_cast<FidTwDD *>(base + o_lo);
+    double2 *d_x = reinterpret_cast<double2 *>(base + o_x), *d_work = reinterpret_cast<double2 *>(base + o_work);
+    double2 *d_z = reinterpret_cast<double2 *>(base + o_z);
+    double *d_u = reinterpret_cast<double *>(base + o_u), *d_v = reinterpret_cast<double *>(base + o_v);
+    double *d_rows = reinterpret_cast<double *>(base + o_rows);
+    double4 *d_part = reinterpret_cast<double4 *>(base + o_part);
+    std::vector<FidJob> jobs(nk);
+    {
+        size_t at_x = 0, at_work = 0, at_z = 0, at_u = 0;
+        for (size_t k = 0; k < nk; ++k) {
+            const int lg = log2_exact(n[k]);
+            const bool is_short = lg <= kLgLds;
+            const size_t total = (size_t)T[k] * (size_t)n[k];
+            jobs[k] = FidJob{d_x + at_x, is_short ? nullptr : d_work + at_work, d_z + at_z, d_u + at_u, d_v + at_u,
+                             d_rows + k * kRow, d_part + p_max[k], (int32_t)n_in[k], (int32_t)n[k], T[k], lg, lg / 2, lg - lg / 2,
+                             (int32_t)(p_max[k + 1] - p_max[k])};
+            at_x += (size_t)T[k] * (size_t)n_in[k];
+            if (!is_short) at_work += total;
+            at_z += total;
+            at_u += (size_t)n[k];
+        }
+    }
+    // (pageable host memory: the copies have left the host arrays when hipMemcpyAsync returns)
+    NMRFIT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), nk * sizeof(FidJob), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_pref, pref.data(), pref.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_tw, tables.stage.data(), kFidStage * sizeof(FidTw), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_hi, tables.hi.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_lo, tables.lo.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_x, fid, (size_t)in_values * sizeof(double2), hipMemcpyHostToDevice, st));
+    const long long *d_short = d_pref, *d_one = d_short + nk + 1, *d_two = d_one + nk + 1, *d_max = d_two + nk + 1,
+                    *d_fin = d_max + nk + 1;
+    const dim3 block(kThreads);
+    const size_t block_lds = 2 * (size_t)kLdsPoints * sizeof(double);
+    if (p_short[nk]) {
+        const int plane = std::max(max_short, 16);   // (swz stays inside an aligned block of 16)
+        hipLaunchKernelGGL(fid_short_kernel, item_grid(p_short[nk]), block, 2 * (size_t)plane * sizeof(double), st, d_jobs, d_short,
+                           (int)K, plane, d_tw);
+        NMRFIT_HIP(hipGetLastError());
+    }
+    if (p_one[nk]) {
+        hipLaunchKernelGGL(fid_pass1_kernel, item_grid(p_one[nk]), block, block_lds, st, d_jobs, d_one, (int)K, d_tw, d_hi, d_lo);
+        NMRFIT_HIP(hipGetLastError());
+        hipLaunchKernelGGL(fid_pass2_kernel, item_grid(p_two[nk]), block, block_lds, st, d_jobs, d_two, (int)K, d_tw);
+        NMRFIT_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(fid_max_part_kernel, item_grid(p_max[nk]), block, 0, st, d_jobs, d_max, (int)K);
+    NMRFIT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), block, 0, st, d_jobs);
+    NMRFIT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fid_finish_kernel, item_grid(p_fin[nk]), block, 0, st, d_jobs, d_fin, (int)K);
+    NMRFIT_HIP(hipGetLastError());
+    if ((rc = staged_d2h(device, st, rows_out, d_rows, nk * kRow * sizeof(double))) != NMRFIT_OK) return rc;
+    if ((rc = staged_d2h(device, st, u_out, d_u, (size_t)points * sizeof(double))) != NMRFIT_OK) return rc;
+    if ((rc = staged_d2h(device, st, v_out, d_v, (size_t)points * sizeof(double))) != NMRFIT_OK) return rc;
+    if (transform_out) return staged_d2h(device, st, transform_out, d_z, (size_t)values * sizeof(double2));
+    return NMRFIT_OK;
+}
+
+#pragma GCC visibility pop

@@ -161,3 +161,55 @@ def jacobian_rows(x, rel_step=1.4901161193847656e-08):
     rows = np.tile(x, (D + 1, 1))
     rows[np.arange(1, D + 1), np.arange(D)] += h
     return rows, h
+
+
+class SynthFid:
+    """What ``make_fid`` returns: ``fid`` (T, n) complex128; ``lines`` as given; ``clean`` (n,) the noise-free trace.
+
+    exact_dft(N)       the DFT of the noise-free trace zero filled to N points, from the geometric series, in long double
+    line_index(f, N)   where a line of frequency f (cycles per point) lies in the OUTPUT order of nmrfit_amd.fid (centred,
+                       then reversed), as a real number: its peak is at the nearest integer"""
+
+    def __init__(self, fid, clean, lines):
+        self.fid, self.clean, self.lines = fid, clean, lines
+
+    def exact_dft(self, N=None):
+        n = self.fid.shape[-1]
+        N = n if N is None else int(N)
+        q = np.arange(N, dtype=np.longdouble)
+        two_pi = 2 * np.arctan2(np.longdouble(0), np.longdouble(-1))
+        X = np.zeros(N, dtype=np.clongdouble)
+        for f, decay, amp, phase in self.lines:
+            f, decay = np.longdouble(f), np.longdouble(decay)
+            # x_j = a z^j with z = exp(2 pi i f - decay): X_q = a (1 - (z w^q)^n) / (1 - z w^q), w = exp(-2 pi i / N)
+            ang = two_pi * (f - q / N)
+            zw = np.exp(-decay) * (np.cos(ang) + 1j * np.sin(ang))
+            ang_n = two_pi * np.fmod(n * (f - q / N), np.longdouble(1))
+            zwn = np.exp(-decay * n) * (np.cos(ang_n) + 1j * np.sin(ang_n))
+            a = np.longdouble(amp) * (np.cos(np.longdouble(phase)) + 1j * np.sin(np.longdouble(phase)))
+            X += a * (1 - zwn) / (1 - zw)
+        return X
+
+    @staticmethod
+    def line_index(f, N):
+        q = (f % 1.0) * N                      # the bin of X
+        i = (q + N // 2) % N                   # after the centring: Y_i = X_{(i + N/2) mod N}
+        return N - 1 - i                       # after the reversal
+
+
+def make_fid(n, lines, T=1, seed=1, noise=0.0, offset=0.0):
+    """A synthetic FID: ``x_j = sum_l a_l exp(i phase_l) exp((2 pi i f_l - d_l) j)``, j = 0 .. n-1, plus complex
+    Gaussian noise of standard deviation ``noise`` per part (a new draw per trace) and a constant ``offset``.
+    ``lines``: tuples (f, d, a[, phase]) -- frequency in cycles per point (-0.5 <= f < 0.5 covers the spectrum),
+    decay per point, amplitude, phase in radians.  Its exact DFT is a geometric series (``SynthFid.exact_dft``): a truth
+    that owes nothing to any FFT, and that says where every line must appear in the output order."""
+    rng = np.random.default_rng(seed)
+    lines = [tuple(ln) + (0.0,) * (4 - len(ln)) for ln in lines]
+    j = np.arange(n)
+    clean = np.zeros(n, dtype=np.complex128)
+    for f, decay, amp, phase in lines:
+        clean += amp * np.exp(1j * phase) * np.exp((2j * np.pi * f - decay) * j)
+    fid = np.tile(clean + offset, (int(T), 1))
+    if noise:
+        fid = fid + noise * (rng.standard_normal((int(T), n)) + 1j * rng.standard_normal((int(T), n)))
+    return SynthFid(fid, clean, lines)
