@@ -3,10 +3,9 @@
 // A part works through its fits in groups that fit the workspace budget (part_normal_equations, part_normal_group: the
 // launches are lsq.hip's); the batch hands every part its share of the caller's arrays (batch_normal_equations), and the
 // two nmrfit_batch_normal_equations* entry points differ in the channel count alone.  nmrfit_batch_sandwich
-// (include/nmrfit_amd_cov.h) is the real channel's call with a Meat: the same groups, one more pair of launches
-// (lsq_cov.hip) on the rows and factors the group has just used; nmrfit_batch_sandwich_im (include/nmrfit_amd_cov_im.h)
-// is the both-channel call with one: four jobs per fit of lsq_cov_im.hip's launches (group_meat_im).  The swarms are not
-// touched.
+// (include/nmrfit_amd_cov.h) and nmrfit_batch_sandwich_im (include/nmrfit_amd_cov_im.h) are those calls with a Meat
+// (batch_sandwich): the same groups, one more pair of launches on the rows and factors the group has just used
+// (group_meat: one job per fit, on both channels four).  The swarms are not touched.
 #include "batch_part.h"
 #include "lsq_internal.h"
 #include "nmrfit_amd_cov.h"
@@ -26,40 +25,38 @@ struct Meat {
     const double *sigma_u, *sigma_v;
     double *M_out;
 };
-// doubles of M_out one fit of D parameters takes
-static int64_t meat_doubles(int64_t D, int nch) { return nch == 2 ? 3 * (D + 1) * (D + 1) : D * D; }
 
-// The two-channel meat of the fits [k0, k1) of a group (lsq_cov_im.hip): jobs are the group's LsqJobs, two per fit (real,
-// imaginary), whose R and c the four meat jobs of the fit read; rows the group's parameter rows (the phase of row 0).
-// One more block of `mem`: [records | segments' sums | M].
-static int group_meat_im(BatchPart *b, int32_t k0, int32_t k1, const LsqJob *jobs, const double *rows, const Meat &meat,
-                         int32_t Dmax, Scratch &mem)
+// The meat of the fits [k0, k1) of a group (launch_lsq_meat): jobs are the group's LsqJobs, nch per fit (real first), whose
+// R and c the meat jobs of the fit read; rows the group's parameter rows (the phase of row 0).  One more block of `mem`:
+// [records | segments' sums | M].
+static int group_meat(BatchPart *b, int32_t k0, int32_t k1, const LsqJob *jobs, const double *rows, const Meat &meat, int32_t Dmax,
+                      int nch, Scratch &mem)
 {
-    const int32_t Kg = k1 - k0;
+    const int32_t Kg = k1 - k0, per = lsq_meat_njobs(nch);
     int64_t n_partial = 0, n_M = 0;
     for (int32_t k = k0; k < k1; ++k) {
-        n_partial += lsq_meat_im_partials(b->Nk[(size_t)k], b->D[(size_t)k]);
-        n_M += meat_doubles(b->D[(size_t)k], 2);
+        n_partial += lsq_meat_partials(b->Nk[(size_t)k], b->D[(size_t)k], nch);
+        n_M += meat_doubles(b->D[(size_t)k], nch);
     }
-    const size_t mrec = align256((size_t)Kg * 4 * sizeof(LsqMeatImJob)) / sizeof(double);
+    const size_t mrec = align256((size_t)Kg * per * sizeof(LsqMeatJob)) / sizeof(double);
     double *d_meat = nullptr;
     NMRFIT_HIP(mem.alloc(&d_meat, mrec + (size_t)(n_partial + n_M)));
     double *d_partial = d_meat + mrec, *d_M = d_partial + n_partial;
-    std::vector<LsqMeatImJob> mjobs((size_t)Kg * 4);
+    std::vector<LsqMeatJob> mjobs((size_t)Kg * per);
     int64_t at_p = 0, at_M = 0, at_x = 0;
     for (int32_t k = k0; k < k1; ++k) {
-        const LsqJob &j = jobs[2 * (k - k0)];   // (the real channel's: its R is the first of the fit's two planes)
+        const LsqJob &j = jobs[nch * (k - k0)];   // (the real channel's: its R is the first of the fit's planes)
         const int64_t D = j.D;
-        lsq_meat_im_jobs(&mjobs[(size_t)(k - k0) * 4], j.R, j.c, b->h_fits[(size_t)k].wt, j.s, rows[at_x], rows[at_x + 1],
-                         meat.sigma_u[k - k0], meat.sigma_v[k - k0], j.N, j.D, d_partial + at_p, d_M + at_M);
-        at_p += lsq_meat_im_partials(j.N, D);
-        at_M += meat_doubles(D, 2);
+        lsq_meat_jobs(&mjobs[(size_t)(k - k0) * per], nch, j.R, j.c, b->h_fits[(size_t)k].wt, j.s, rows[at_x], rows[at_x + 1],
+                      meat.sigma_u[k - k0], meat.sigma_v[k - k0], j.N, j.D, d_partial + at_p, d_M + at_M);
+        at_p += lsq_meat_partials(j.N, D, nch);
+        at_M += meat_doubles(D, nch);
         at_x += (D + 1) * D;
     }
     hipStream_t st = b->stream;
     // (pageable host memory: the copy has left `mjobs` when hipMemcpyAsync returns)
-    NMRFIT_HIP(hipMemcpyAsync(d_meat, mjobs.data(), mjobs.size() * sizeof(LsqMeatImJob), hipMemcpyHostToDevice, st));
-    const int rc = launch_lsq_meat_im(st, reinterpret_cast<const LsqMeatImJob *>(d_meat), 4 * Kg, Dmax);
+    NMRFIT_HIP(hipMemcpyAsync(d_meat, mjobs.data(), mjobs.size() * sizeof(LsqMeatJob), hipMemcpyHostToDevice, st));
+    const int rc = launch_lsq_meat(st, reinterpret_cast<const LsqMeatJob *>(d_meat), per * Kg, Dmax, nch);
     if (rc != NMRFIT_OK) return rc;
     NMRFIT_HIP(hipMemcpyAsync(meat.M_out, d_M, (size_t)n_M * sizeof(double), hipMemcpyDeviceToHost, st));
     return NMRFIT_OK;
@@ -158,48 +155,7 @@ static int part_normal_group(BatchPart *b, int32_t k0, int32_t k1, size_t lds, u
     int rc = launch_rows_batch(st, d_fits, Kg, Smax, lds, aux_off, fit_im);
     if (rc != NMRFIT_OK) return rc;
     if (sums && (rc = launch_lsq(st, d_jobs, nch * Kg, Dmax, true)) != NMRFIT_OK) return rc;
-    if (meat && meat->M_out && fit_im) {
-        if ((rc = group_meat_im(b, k0, k1, jobs, rows, *meat, Dmax, mem)) != NMRFIT_OK) return rc;
-    } else if (meat && meat->M_out) {
-        // the meat of every fit (real channel alone: job k - k0 is fit k's): R and c where the fit's LsqJob has them, the
-        // fit's resident weights, the phase of its row 0; one more block of `mem`: [records | segments' sums | M]
-        int64_t n_mpartial = 0;
-        for (int32_t k = k0; k < k1; ++k) n_mpartial += jobs[k - k0].nseg * (lsq_sums(b->D[(size_t)k]) - b->D[(size_t)k]);
-        const int64_t n_M = n_rows - n_c;   // sum of D^2
-        const size_t mrec = align256((size_t)Kg * sizeof(LsqMeatJob)) / sizeof(double);
-        double *d_meat = nullptr;
-        NMRFIT_HIP(mem.alloc(&d_meat, mrec + (size_t)(n_mpartial + n_M)));
-        double *d_mpartial = d_meat + mrec, *d_M = d_mpartial + n_mpartial;
-        std::vector<LsqMeatJob> mjobs((size_t)Kg);
-        int64_t at_mp = 0, at_M = 0, at_x = 0;
-        for (int32_t k = k0; k < k1; ++k) {
-            const LsqJob &j = jobs[k - k0];
-            const int64_t D = j.D;
-            LsqMeatJob &m = mjobs[(size_t)(k - k0)];
-            m = LsqMeatJob{};
-            m.R = j.R;
-            m.c = j.c;
-            m.wt = b->h_fits[(size_t)k].wt;
-            m.s = j.s;
-            m.p0 = rows[at_x];
-            m.p1 = rows[at_x + 1];
-            m.var_u = meat->sigma_u[k - k0] * meat->sigma_u[k - k0];
-            m.var_v = meat->sigma_v[k - k0] * meat->sigma_v[k - k0];
-            m.N = j.N;
-            m.D = j.D;
-            m.nseg = j.nseg;
-            m.seg_tiles = j.seg_tiles;
-            m.partial = d_mpartial + at_mp;
-            m.M = d_M + at_M;
-            at_mp += j.nseg * (lsq_sums(D) - D);
-            at_M += D * D;
-            at_x += (D + 1) * D;
-        }
-        // (pageable host memory: the copy has left `mjobs` when hipMemcpyAsync returns)
-        NMRFIT_HIP(hipMemcpyAsync(d_meat, mjobs.data(), mjobs.size() * sizeof(LsqMeatJob), hipMemcpyHostToDevice, st));
-        if ((rc = launch_lsq_meat(st, reinterpret_cast<const LsqMeatJob *>(d_meat), Kg, Dmax)) != NMRFIT_OK) return rc;
-        NMRFIT_HIP(hipMemcpyAsync(meat->M_out, d_M, (size_t)n_M * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
+    if (meat && meat->M_out && (rc = group_meat(b, k0, k1, jobs, rows, *meat, Dmax, nch, mem)) != NMRFIT_OK) return rc;
     if (A_out) NMRFIT_HIP(hipMemcpyAsync(A_out, d_A, (size_t)n_A * sizeof(double), hipMemcpyDeviceToHost, st));
     if (g_out) NMRFIT_HIP(hipMemcpyAsync(g_out, d_g, (size_t)(nch * n_c) * sizeof(double), hipMemcpyDeviceToHost, st));
     std::vector<double> fall(f_out ? (size_t)n_f : 0);
@@ -317,46 +273,40 @@ int nmrfit_batch_normal_equations_im(nmrfit_batch *b, const double *rows, const 
     return batch_normal_equations(b, "nmrfit_batch_normal_equations_im", 2, rows, c, s, A_out, g_out, f2_out);
 }
 
-// include/nmrfit_amd_cov.h.  Every refusal comes before the first launch: the batch is as it was.
-int nmrfit_batch_sandwich(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
-                          const double *sigma_v, double *A_out, double *M_out, double *g_out, double *f_out)
+// include/nmrfit_amd_cov.h and nmrfit_amd_cov_im.h.  Every refusal comes before the first launch: the batch is as it was.
+static int batch_sandwich(nmrfit_batch *b, const char *who, int nch, const double *rows, const double *c, const double *s,
+                          const double *sigma_u, const double *sigma_v, double *A_out, double *g_out, double *f_out, double *M_out)
 {
     int rc = check_batch_handle(b);
     if (rc != NMRFIT_OK) return rc;
     if (!rows || !c || !s || !sigma_u || !sigma_v)
-        return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich: null rows, c, s, sigma_u or sigma_v");
+        return refuse(NMRFIT_E_INVALID, std::string(who) + ": null rows, c, s, sigma_u or sigma_v");
     for (int32_t k = 0; k < b->K; ++k)
-        if ((rc = check_sigma("nmrfit_batch_sandwich", sigma_u[k], sigma_v[k])) != NMRFIT_OK) return rc;
+        if ((rc = check_sigma(who, sigma_u[k], sigma_v[k])) != NMRFIT_OK) return rc;
     for (const BatchPart *p : b->parts) {
-        if (p->fit_im != NMRFIT_FIT_IM_OFF)
+        if (nch == 1 && p->fit_im != NMRFIT_FIT_IM_OFF)
             return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich: the batch was created with a fit_im mode: its fits minimise "
                                                 "a mean of two norms, which this covariance does not describe");
-        if (4 + 3 * (int64_t)p->Pmax > kLsqMaxD)
-            return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich: D = 4 + 3 P <= " + std::to_string(kLsqMaxD) + " for every fit");
-    }
-    const Meat meat{sigma_u, sigma_v, M_out};
-    return batch_normal_equations(b, "nmrfit_batch_sandwich", 1, rows, c, s, A_out, g_out, f_out, &meat);
-}
-
-// include/nmrfit_amd_cov_im.h.  Every refusal comes before the first launch: the batch is as it was.
-int nmrfit_batch_sandwich_im(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
-                             const double *sigma_v, double *A_out, double *g_out, double *rho_out, double *M_out)
-{
-    int rc = check_batch_handle(b);
-    if (rc != NMRFIT_OK) return rc;
-    if (!rows || !c || !s || !sigma_u || !sigma_v)
-        return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich_im: null rows, c, s, sigma_u or sigma_v");
-    for (int32_t k = 0; k < b->K; ++k)
-        if ((rc = check_sigma("nmrfit_batch_sandwich_im", sigma_u[k], sigma_v[k])) != NMRFIT_OK) return rc;
-    for (const BatchPart *p : b->parts) {
-        if (p->fit_im != NMRFIT_FIT_IM_REFERENCE && p->fit_im != NMRFIT_FIT_IM_SUM)
+        if (nch == 2 && p->fit_im != NMRFIT_FIT_IM_REFERENCE && p->fit_im != NMRFIT_FIT_IM_SUM)
             return refuse(NMRFIT_E_INVALID, "nmrfit_batch_sandwich_im: the batch was created with fit_im = 0 (real part only): "
                                             "nmrfit_batch_sandwich is the call for it");
         if (4 + 3 * (int64_t)p->Pmax > kLsqMaxD)
-            return refuse(NMRFIT_E_UNSUPPORTED, "nmrfit_batch_sandwich_im: D = 4 + 3 P <= " + std::to_string(kLsqMaxD) + " for every fit");
+            return refuse(NMRFIT_E_UNSUPPORTED, std::string(who) + ": D = 4 + 3 P <= " + std::to_string(kLsqMaxD) + " for every fit");
     }
     const Meat meat{sigma_u, sigma_v, M_out};
-    return batch_normal_equations(b, "nmrfit_batch_sandwich_im", 2, rows, c, s, A_out, g_out, rho_out, &meat);
+    return batch_normal_equations(b, who, nch, rows, c, s, A_out, g_out, f_out, &meat);
+}
+
+int nmrfit_batch_sandwich(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
+                          const double *sigma_v, double *A_out, double *M_out, double *g_out, double *f_out)
+{
+    return batch_sandwich(b, "nmrfit_batch_sandwich", 1, rows, c, s, sigma_u, sigma_v, A_out, g_out, f_out, M_out);
+}
+
+int nmrfit_batch_sandwich_im(nmrfit_batch *b, const double *rows, const double *c, const double *s, const double *sigma_u,
+                             const double *sigma_v, double *A_out, double *g_out, double *rho_out, double *M_out)
+{
+    return batch_sandwich(b, "nmrfit_batch_sandwich_im", 2, rows, c, s, sigma_u, sigma_v, A_out, g_out, rho_out, M_out);
 }
 
 }  // extern "C"

@@ -2,24 +2,10 @@
 // are already in device memory, the forward-difference Jacobian J (N x D, the layout scipy receives), the residual r, and
 // the normal equations A = J^T J, g = J^T r; plus the residual-rows launch over every fit of a resident batch.
 //
-// lsq_normal_kernel: a workgroup owns a SEGMENT of the grid (whole tiles of 64 points; at most 64 segments per fit, a
-// function of N alone).  Per tile it forms T[j][0..D) = (R[i + 1][j] - R[0][j]) * c_i and T[j][D] = R[0][j] * s in LDS --
-// the row loads coalesced along the grid, the LDS rows at an ODD pitch so that the 64 lanes of a load (64 different j)
-// hit 64 different bank pairs -- writes the tile of J as ONE contiguous run of 64 D doubles (row-major N x D: the tile's
-// rows follow each other in memory) and r, and then every thread adds the tile's 64 products to the (up to) twelve
-// entries of the upper triangle of A / of g it owns, in registers, point after point.  A and g are the same thing to
-// the kernel: g_i is the "pair" (i, D).  The per-segment sums go to memory; lsq_reduce_kernel adds them segment after
-// segment and mirrors the triangle.  Every sum has ONE order, fixed by N: no atomics, nothing depends on scheduling.
-//
-// The products are plain fp64 FMAs, not v_mfma_f64_16x16x4_f64: D = 4 + 3 P is never a multiple of 16 (76 = 4.75
-// blocks: a quarter of the last block row and column would multiply padding), the contraction is N D^2 / 2 = 47 MFLOP at
-// the C5 shape -- microseconds next to the rows launch before it, which evaluates (D + 1) N P Voigt profiles -- and
-// with scalar FMAs the order of every sum is written down in the loop below, which is what the bit-for-bit
-// requirements rest on.  
-//
-// J and r equal the host's expressions bit for bit: `(a - b) * c` has nothing added to the product, so -ffp-contract=on
-// finds nothing to fuse.
-#include "lsq_internal.h"
+// lsq_normal_kernel is the stages of lsq_tile.h -- which states the plan -- with J and r written out of the tile: the tile
+// of J as ONE contiguous run of 64 D doubles (row-major N x D: the tile's rows follow each other in memory).  A and g are
+// the same thing to the kernel: g_i is the "pair" (i, D).  
+#include "lsq_tile.h"
 #include "objective_kernel.h"
 
 namespace nmrfit {
@@ -32,33 +18,23 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_normal_kernel(const LsqJob *_
     if ((int)blockIdx.x >= q.nseg) return;   // (a batch's launch is as wide as its longest grid needs)
     const int D = q.D, pitch = (D + 1) | 1;
     const int64_t N = q.N;
-    const int tid = threadIdx.x, jl = tid & (kLsqTile - 1), i0 = tid >> 6;
+    const int tid = threadIdx.x, jl = tid & (kLsqTile - 1);
+    // (the wave's index where the compiler can see that it is one value per wave: the column loop of lsq_form then counts in
+    // scalar registers -- 132 VGPRs; with `tid >> 6` 138, above the kernel's bar of 136.  The meat kernels have no scalar
+    // registers to spare for it: lsq_meat_im_kernel would park six in vector lanes)
+    const int i0 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool sums = q.partial != nullptr;
     const int nout = sums ? D * (D + 1) / 2 + D : 0;
     int pa[kLsqAcc], pb[kLsqAcc];
     double acc[kLsqAcc];
-#pragma unroll
-    for (int m = 0; m < kLsqAcc; ++m) {
-        const int o = tid + m * kLsqThreads;
-        pa[m] = pb[m] = 0;
-        if (o < nout) lsq_pair(o, D, &pa[m], &pb[m]);
-        acc[m] = 0.0;
-    }
-    const int64_t tiles = (N + kLsqTile - 1) / kLsqTile;
-    const int64_t t0 = (int64_t)blockIdx.x * q.seg_tiles;
-    const int64_t t1 = (t0 + q.seg_tiles < tiles) ? t0 + q.seg_tiles : tiles;
-    const double *__restrict__ R = q.R;
-    const double *__restrict__ c = q.c;
+    lsq_own_pairs(nout, [D](int o, int *a, int *b) { lsq_pair(o, D, a, b); }, pa, pb, acc);
+    int64_t t0, t1;
+    lsq_tile_range(N, q.seg_tiles, &t0, &t1);
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t j0 = t * kLsqTile;
         const int nj = (int)((N - j0 < kLsqTile) ? N - j0 : kLsqTile);
         const bool have = jl < nj;
-        const double r0 = have ? R[j0 + jl] : 0.0;
-        for (int i = i0; i < D; i += kLsqThreads / kLsqTile) {
-            const double ri = have ? R[(int64_t)(i + 1) * N + j0 + jl] : 0.0;
-            T[jl * pitch + i] = (ri - r0) * c[i];
-        }
-        if (i0 == 0) T[jl * pitch + D] = r0 * q.s;
+        lsq_form(T, pitch, q.R, q.c, q.s, N, D, j0, have, i0, 0, D + 1);
         __syncthreads();
         if (q.J) {   // rows j0 .. j0 + nj of the row-major N x D matrix: nj D consecutive doubles
             double *__restrict__ Jt = q.J + j0 * D;
@@ -68,23 +44,10 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_normal_kernel(const LsqJob *_
             }
         }
         if (q.r && i0 == 0 && have) q.r[j0 + jl] = T[jl * pitch + D];
-        if (sums) {
-            for (int jj = 0; jj < nj; ++jj) {
-                const double *row = T + jj * pitch;
-#pragma unroll
-                for (int m = 0; m < kLsqAcc; ++m) acc[m] = __builtin_fma(row[pa[m]], row[pb[m]], acc[m]);
-            }
-        }
+        if (sums) lsq_accumulate<false>(T, pitch, T, pitch, nullptr, nj, pa, pb, acc);
         __syncthreads();
     }
-    if (sums) {
-        double *__restrict__ out = q.partial + (int64_t)blockIdx.x * nout;
-#pragma unroll
-        for (int m = 0; m < kLsqAcc; ++m) {
-            const int o = tid + m * kLsqThreads;
-            if (o < nout) out[o] = acc[m];
-        }
-    }
+    if (sums) lsq_store_partial(q.partial, nout, acc);
 }
 
 // the segments' sums one after the other, segment 0 first; A comes back whole (both triangles from the same sum)
@@ -94,8 +57,7 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_reduce_kernel(const LsqJob *_
     if (!q.partial) return;
     const int D = q.D, nout = D * (D + 1) / 2 + D;
     for (int o = threadIdx.x; o < nout; o += kLsqThreads) {
-        double sum = 0.0;
-        for (int sgm = 0; sgm < q.nseg; ++sgm) sum += q.partial[(int64_t)sgm * nout + o];
+        const double sum = lsq_segment_sum(q.partial, q.nseg, nout, o);
         int a, b;
         lsq_pair(o, D, &a, &b);
         if (b == D) {

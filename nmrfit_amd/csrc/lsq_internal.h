@@ -1,7 +1,7 @@
 // lsq_internal.h -- shared by lsq.hip (the kernels of include/nmrfit_amd_lsq.h), lsq_cov.hip (those of
-// include/nmrfit_amd_cov.h, nmrfit_sandwich), lsq_cov_im.hip (those of include/nmrfit_amd_cov_im.h, nmrfit_sandwich_im),
-// ctx_eval.hip (nmrfit_jacobian*) and batch_lsq.hip (nmrfit_batch_normal_equations*, nmrfit_batch_sandwich*): the per-fit
-// records the kernels read and the launches.
+// include/nmrfit_amd_cov.h, nmrfit_sandwich*), lsq_cov_im.hip (those of include/nmrfit_amd_cov_im.h), ctx_eval.hip
+// (nmrfit_jacobian*) and batch_lsq.hip (nmrfit_batch_normal_equations*, nmrfit_batch_sandwich*): the per-fit records the
+// kernels read and the launches.
 #pragma once
 #include "nmrfit_amd_lsq.h"
 #include "nmrfit_amd_lsq_im.h"
@@ -64,59 +64,46 @@ __device__ __forceinline__ void lsq_pair(int o, int D, int *a, int *b)
 // J, r and -- where a job has `partial` -- A and g of K fits (jobs: device memory), on `st`.  Dmax <= kLsqMaxD.
 int launch_lsq(hipStream_t st, const LsqJob *d_jobs, int32_t K, int32_t Dmax, bool sums);
 
-// One fit of a meat launch (lsq_cov.hip, include/nmrfit_amd_cov.h): R and c as its LsqJob has them, the fit's resident
-// weights (grid_slot order, padded to whole chunks), the phase of row 0 and the two channels' noise variances.
+// One job of a meat launch (lsq_cov.hip, lsq_cov_im.hip; the stages: lsq_tile.h): one block of
+// Mt_ab = Jt_a^T diag(q_ab) Jt_b.  A fit on the real channel (include/nmrfit_amd_cov.h) is ONE job, kind rr, of D columns:
+// Jt = J, Ra = Rb = its residual rows, M = J^T diag(q) J.  A fit on both channels (include/nmrfit_amd_cov_im.h) is FOUR,
+// of C = D + 1 columns, Jt_ch = [J_ch | r_ch]: (re, re) and (im, im), the upper triangle of a symmetric block each, and
+// (re, im) in two bands of rows.  lsq_meat_kernel reads neither kind, rows nor Ra.
+enum { kMeatRR = 0, kMeatII = 1, kMeatRI = 2 };
 struct LsqMeatJob {
-    const double *R;
-    const double *c;
-    const double *wt;
-    double s, p0, p1;
-    double var_u, var_v;   // sigma_u^2, sigma_v^2
-    int64_t N;
-    int32_t D;
-    int32_t nseg, seg_tiles;   // lsq_segments(N)
-    int32_t pad;
-    double *partial;       // nseg x D (D + 1) / 2
-    double *M;             // D x D
-};
-// M = J^T diag(q) J of K fits (jobs: device memory), on `st`, after the rows launch that made every R.  Dmax <= kLsqMaxD.
-int launch_lsq_meat(hipStream_t st, const LsqMeatJob *d_jobs, int32_t K, int32_t Dmax);
-// NMRFIT_E_INVALID unless both are finite and >= 0
-int check_sigma(const char *who, double sigma_u, double sigma_v);
-
-// One job of a two-channel meat launch (lsq_cov_im.hip, include/nmrfit_amd_cov_im.h): one block of
-// Mt_ab = Jt_a^T diag(q_ab) Jt_b with Jt_ch = [J_ch | r_ch], C = D + 1 columns.  A fit is four jobs (lsq_meat_im_jobs):
-// (re, re) and (im, im), the upper triangle of a symmetric block each, and (re, im) in two bands of rows.
-enum { kMeatImRR = 0, kMeatImII = 1, kMeatImRI = 2 };
-struct LsqMeatImJob {
     const double *Ra;      // the D + 1 residual rows of channel a (the rows of the block), N doubles each
     const double *Rb;      // those of channel b (its columns); Ra for a symmetric kind
-    const double *c;
-    const double *wt;
-    double s, p0, p1;
-    double var_u, var_v;   // sigma_u^2, sigma_v^2 (kMeatImRI: sigma_u^2 - sigma_v^2 in var_u, var_v unused)
+    const double *c;       // as the fit's LsqJob has it
+    const double *wt;      // the fit's resident weights (grid_slot order, padded to whole chunks)
+    double s, p0, p1;      // p0, p1: the phase of row 0
+    double var_u, var_v;   // sigma_u^2, sigma_v^2 (kMeatRI: sigma_u^2 - sigma_v^2 in var_u, var_v unused)
     int64_t N;
     int32_t D;
     int32_t nseg, seg_tiles;   // lsq_segments(N)
-    int32_t kind;          // kMeatIm*
-    int32_t row0, row1;    // kMeatImRI: the job's rows [row0, row1) of the block; else 0, C
-    double *partial;       // nseg x lsq_meat_im_sums(job)
-    double *M;             // the C x C block, row-major
+    int32_t kind;          // kMeat*
+    int32_t row0, row1;    // kMeatRI: the job's rows [row0, row1) of the block; else 0, the columns
+    double *partial;       // nseg x the sums one segment leaves: a triangle of the columns, or every entry of the band
+    double *M;             // the block, row-major
 };
-// the sums one segment of a job leaves: the upper triangle of a symmetric block, every entry of a band of the cross block
-inline int64_t lsq_meat_im_sums(const LsqMeatImJob &j)
-{
-    const int64_t C = j.D + 1;
-    return j.kind == kMeatImRI ? (j.row1 - j.row0) * C : C * (C + 1) / 2;
-}
-// doubles of segment sums the four jobs of one fit need
-int64_t lsq_meat_im_partials(int64_t N, int64_t D);
-// the four jobs of one fit: R its [2][D + 1][N] residual rows (real plane first), partial lsq_meat_im_partials(N, D) doubles,
-// M [3][C x C]: the blocks rr, ii, ri
-void lsq_meat_im_jobs(LsqMeatImJob job[4], const double *R, const double *c, const double *wt, double s, double p0, double p1,
-                      double sigma_u, double sigma_v, int64_t N, int32_t D, double *partial, double *M);
-// the blocks of njobs jobs (device memory), on `st`, after the both-channel rows launch that made every R.  Dmax <= kLsqMaxD.
-int launch_lsq_meat_im(hipStream_t st, const LsqMeatImJob *d_jobs, int32_t njobs, int32_t Dmax);
+inline int lsq_meat_njobs(int nch) { return nch == 2 ? 4 : 1; }
+// the rows of the cross block's first band: the second takes the rest
+inline int32_t cross_split(int32_t C) { return (C + 1) / 2; }
+static_assert(kLsqThreads * kLsqAcc >= (kLsqMaxD + 1) * (kLsqMaxD + 2) / 2, "accumulators for a symmetric block of the largest D");
+static_assert(kLsqThreads * kLsqAcc >= ((kLsqMaxD + 2) / 2) * (kLsqMaxD + 1), "accumulators for a band of the cross block");
+// doubles of M one fit of D parameters takes: D x D, or on both channels [3][C x C], the blocks rr, ii, ri
+inline int64_t meat_doubles(int64_t D, int nch) { return nch == 2 ? 3 * (D + 1) * (D + 1) : D * D; }
+// doubles of segment sums the jobs of one fit need
+int64_t lsq_meat_partials(int64_t N, int64_t D, int nch);
+// the lsq_meat_njobs(nch) jobs of one fit: R its [nch][D + 1][N] residual rows (real plane first), partial
+// lsq_meat_partials(N, D, nch) doubles -- the jobs' sums in job order -- and M meat_doubles(D, nch)
+void lsq_meat_jobs(LsqMeatJob *job, int nch, const double *R, const double *c, const double *wt, double s, double p0, double p1,
+                   double sigma_u, double sigma_v, int64_t N, int32_t D, double *partial, double *M);
+// the blocks of njobs jobs of nch channels (device memory), on `st`, after the rows launch that made every R: the kernel
+// pair and the LDS of the channel count.  Dmax <= kLsqMaxD.
+int launch_lsq_meat(hipStream_t st, const LsqMeatJob *d_jobs, int32_t njobs, int32_t Dmax, int nch);
+int launch_lsq_meat_im_kernels(hipStream_t st, const LsqMeatJob *d_jobs, int32_t njobs, int32_t Dmax);   // (lsq_cov_im.hip's half of it)
+// NMRFIT_E_INVALID unless both are finite and >= 0
+int check_sigma(const char *who, double sigma_u, double sigma_v);
 // J and r alone for one fit of any D (no LDS tile): what nmrfit_jacobian runs beyond kLsqMaxD
 int launch_lsq_plain(hipStream_t st, const LsqJob &job);
 
