@@ -206,6 +206,11 @@ COV_IM_SIGNATURES = {
 FID_SIGNATURES = {
     "nmrfit_fid_transform": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# FID_COND_SIGNATURES: include/nmrfit_amd_fid_cond.h (the same with the conditioning between the FID and the transform: the
+# removal of a Bruker group delay, a window)
+FID_COND_SIGNATURES = {
+    "nmrfit_fid_condition_transform": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                 # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -311,7 +316,7 @@ def lib():
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
                 + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
                 + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()) \
-                + list(FID_SIGNATURES.items()):
+                + list(FID_SIGNATURES.items()) + list(FID_COND_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -29,8 +29,8 @@
 // thread writes.  Radix 4 keeps 4 butterflies x 4 points (64 VGPRs of data) per thread at 4096 points and halves the
 // stages, and with them the barriers and the LDS traffic, against radix 2; an odd log2 L takes ONE radix-2 stage first
 // (its twiddles are all 1).
-#include "fid_twiddle.h"
-#include "host_call.h"
+#include "fid_device.h"
+#include "fid_internal.h"
 #include "nmrfit_amd_fid.h"
 #include "weights_internal.h"
 
@@ -55,48 +55,11 @@ constexpr unsigned kGridX = 32768;   // work items per grid row (an item is bloc
 static_assert(kLgLds == kFidLgStage && kLgMax == kFidLgMax, "the twiddle tables are sized for these lengths");
 static_assert(kLgMax <= 2 * (kLgLds - 1), "both factors of a long transform leave at least two transforms per block");
 
-// One spectrum of a call.  Every pointer is device memory.
-struct FidJob {
-    const double2 *x;    // T traces of n_in points
-    double2 *work;       // T traces of n points between the passes (n > 4096)
-    double2 *z;          // T traces of n points: Y in the output order
-    double *u, *v;       // n points each
-    double *row;         // [kRow]
-    double4 *part;       // the partial maxima: (re, im, flat index, not-finite flag)
-    int32_t n_in, n, T, lg, lg1, lg2, parts;
-};
-
-struct Cx {
-    double re, im;
-};
-__device__ __forceinline__ Cx cmul(Cx a, Cx w) { return Cx{a.re * w.re - a.im * w.im, a.re * w.im + a.im * w.re}; }
-__device__ __forceinline__ Cx cadd(Cx a, Cx b) { return Cx{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ Cx csub(Cx a, Cx b) { return Cx{a.re - b.re, a.im - b.im}; }
-
 // where index a of the block lies in a plane (the header comment: THE LDS BLOCK)
 __device__ __forceinline__ int swz(int a)
 {
     const int h = a >> 4;
     return a ^ ((-(h & 1) & 15) ^ (-((h >> 1) & 1) & 10) ^ ((h >> 2) & 7));
-}
-
-// the work item of this workgroup, or -1 past the end (the whole workgroup leaves)
-__device__ __forceinline__ long long work_item(long long total)
-{
-    const long long item = (long long)blockIdx.y * gridDim.x + blockIdx.x;
-    return item < total ? item : -1;
-}
-
-// the spectrum of an item: the largest k < K with pref[k] <= item (a spectrum without items has pref[k] == pref[k + 1])
-__device__ __forceinline__ int find_job(const long long *__restrict__ pref, int K, long long item)
-{
-    int lo = 0, hi = K;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pref[mid] <= item) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // One in-place stage of radix R on M = C L points: Ns = 2^lgNs points of every transform are transformed already.
@@ -382,13 +345,18 @@ const FidTables &fid_tables()
     return t;
 }
 
-dim3 item_grid(long long items)
+
+}  // namespace
+
+// ---- the pieces of a call (fid_internal.h) --------------------------------------------------------------------------
+
+dim3 fid_item_grid(long long items)
 {
     const unsigned gx = (unsigned)std::min<long long>(items, kGridX);
     return dim3(gx, (unsigned)((items + gx - 1) / gx));
 }
 
-int log2_exact(int64_t n)   // -1 unless n is a power of two
+int fid_log2_exact(int64_t n)
 {
     if (n <= 0 || (n & (n - 1))) return -1;
     int lg = 0;
@@ -396,7 +364,104 @@ int log2_exact(int64_t n)   // -1 unless n is a power of two
     return lg;
 }
 
-}  // namespace
+FidPlan fid_plan(const FidShape *shapes, size_t nk)
+{
+    FidPlan plan;
+    plan.K = nk;
+    plan.pref.assign((size_t)kFidLaunchTables * (nk + 1), 0);
+    long long *p_short = plan.pref.data(), *p_one = p_short + nk + 1, *p_two = p_one + nk + 1, *p_max = p_two + nk + 1,
+              *p_fin = p_max + nk + 1;
+    for (size_t k = 0; k < nk; ++k) {
+        const int64_t n = shapes[k].n;
+        const int lg = fid_log2_exact(n);
+        const bool is_short = lg <= kLgLds;
+        const int lg1 = lg / 2, lg2 = lg - lg1;
+        const long long Tk = shapes[k].T, total = Tk * n;
+        p_short[k + 1] = p_short[k] + (is_short ? Tk : 0);
+        p_one[k + 1] = p_one[k] + (is_short ? 0 : Tk << (lg2 - (kLgLds - lg1)));
+        p_two[k + 1] = p_two[k] + (is_short ? 0 : Tk << (lg1 - (kLgLds - lg2)));
+        p_max[k + 1] = p_max[k] + (total + kMaxChunk - 1) / kMaxChunk;
+        p_fin[k + 1] = p_fin[k] + (n + kFinishChunk - 1) / kFinishChunk;
+        if (is_short) plan.max_short = std::max(plan.max_short, (int)n);
+        else plan.work_values += total;
+        plan.values += total;
+        plan.in_values += Tk * shapes[k].n_in;
+        plan.points += n;
+    }
+    return plan;
+}
+
+std::vector<FidJob> fid_job_table(const FidPlan &plan, const FidShape *shapes, const double2 *const *x_of, const FidBuffers &buf)
+{
+    const size_t nk = plan.K;
+    const long long *p_max = plan.table(kFidMaxPart);
+    std::vector<FidJob> jobs(nk);
+    size_t at_work = 0, at_z = 0, at_u = 0;
+    for (size_t k = 0; k < nk; ++k) {
+        const int lg = fid_log2_exact(shapes[k].n);
+        const bool is_short = lg <= kLgLds;
+        const size_t total = (size_t)shapes[k].T * (size_t)shapes[k].n;
+        jobs[k] = FidJob{x_of[k], is_short ? nullptr : buf.work + at_work, buf.z + at_z, buf.u ? buf.u + at_u : nullptr,
+                         buf.v ? buf.v + at_u : nullptr, buf.rows ? buf.rows + k * kRow : nullptr, buf.part ? buf.part + p_max[k] : nullptr,
+                         (int32_t)shapes[k].n_in, (int32_t)shapes[k].n, shapes[k].T, lg, lg / 2, lg - lg / 2,
+                         (int32_t)(p_max[k + 1] - p_max[k])};
+        if (!is_short) at_work += total;
+        at_z += total;
+        at_u += (size_t)shapes[k].n;
+    }
+    return jobs;
+}
+
+hipError_t fid_upload_tables(const FidDeviceTables &dst, hipStream_t st)
+{
+    const FidTables &tables = fid_tables();
+    hipError_t e = hipMemcpyAsync(dst.tw, tables.stage.data(), kFidStage * sizeof(FidTw), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(dst.hi, tables.hi.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(dst.lo, tables.lo.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st);
+}
+
+hipError_t fid_launch_transforms(const FidPlan &plan, const FidJob *d_jobs, const long long *d_pref, const FidDeviceTables &tables,
+                                 hipStream_t st)
+{
+    const size_t nk = plan.K;
+    const int K = (int)nk;
+    const long long *d_short = d_pref, *d_one = d_short + nk + 1, *d_two = d_one + nk + 1;
+    const dim3 block(kThreads);
+    const size_t block_lds = 2 * (size_t)kLdsPoints * sizeof(double);
+    hipError_t e;
+    if (plan.items(kFidShort)) {
+        const int plane = std::max(plan.max_short, 16);   // (swz stays inside an aligned block of 16)
+        hipLaunchKernelGGL(fid_short_kernel, fid_item_grid(plan.items(kFidShort)), block, 2 * (size_t)plane * sizeof(double), st, d_jobs,
+                           d_short, K, plane, tables.tw);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (plan.items(kFidPass1)) {
+        hipLaunchKernelGGL(fid_pass1_kernel, fid_item_grid(plan.items(kFidPass1)), block, block_lds, st, d_jobs, d_one, K, tables.tw,
+                           tables.hi, tables.lo);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(fid_pass2_kernel, fid_item_grid(plan.items(kFidPass2)), block, block_lds, st, d_jobs, d_two, K, tables.tw);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t fid_launch_finish(const FidPlan &plan, const FidJob *d_jobs, const long long *d_pref, hipStream_t st)
+{
+    const size_t nk = plan.K;
+    const int K = (int)nk;
+    const long long *d_max = d_pref + (size_t)kFidMaxPart * (nk + 1), *d_fin = d_pref + (size_t)kFidFinish * (nk + 1);
+    const dim3 block(kThreads);
+    hipError_t e;
+    hipLaunchKernelGGL(fid_max_part_kernel, fid_item_grid(plan.items(kFidMaxPart)), block, 0, st, d_jobs, d_max, K);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), block, 0, st, d_jobs);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(fid_finish_kernel, fid_item_grid(plan.items(kFidFinish)), block, 0, st, d_jobs, d_fin, K);
+    return hipGetLastError();
+}
+
 }  // namespace nmrfit
 
 using namespace nmrfit;
@@ -416,17 +481,13 @@ int nmrfit_fid_transform(int device, int32_t K, const int64_t *n_in, const int64
             return refuse(NMRFIT_E_INVALID, who + ": a transform length is at least the trace's length (spectrum " + std::to_string(k) + ")");
     }
     const int64_t max_values = (int64_t)1 << 26;
-    int64_t values = 0, points = 0, in_values = 0;
+    int64_t values = 0;
     for (int32_t k = 0; k < K; ++k) {
-        const int lg = log2_exact(n[k]);
+        const int lg = fid_log2_exact(n[k]);
         if (lg < 1 || lg > kLgMax)
             return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
                                                     " (spectrum " + std::to_string(k) + "): zero fill to the next power of two");
-        if (values <= max_values) {   // (each term < 2^53: the sums cannot overflow)
-            values += (int64_t)T[k] * n[k];
-            in_values += (int64_t)T[k] * n_in[k];
-        }
-        points += n[k];
+        if (values <= max_values) values += (int64_t)T[k] * n[k];   // (each term < 2^53: the sum cannot overflow)
     }
     if (K > kWeightsMaxSpectra || values > max_values)
         return refuse(NMRFIT_E_UNSUPPORTED, who + ": a call takes at most " + std::to_string(kWeightsMaxSpectra) + " spectra and " +
@@ -437,96 +498,49 @@ int nmrfit_fid_transform(int device, int32_t K, const int64_t *n_in, const int64
     NMRFIT_HIP(lease.take());
     hipStream_t st = lease.s;
 
-    // the work items of every launch: prefix tables over the spectra
     const size_t nk = (size_t)K;
-    std::vector<long long> pref(5 * (nk + 1), 0);
-    long long *p_short = pref.data(), *p_one = p_short + nk + 1, *p_two = p_one + nk + 1, *p_max = p_two + nk + 1,
-              *p_fin = p_max + nk + 1;
-    int64_t work_values = 0;
-    int max_short = 0;
-    for (size_t k = 0; k < nk; ++k) {
-        const int lg = log2_exact(n[k]);
-        const bool is_short = lg <= kLgLds;
-        const int lg1 = lg / 2, lg2 = lg - lg1;
-        const long long Tk = T[k], total = Tk * n[k];
-        p_short[k + 1] = p_short[k] + (is_short ? Tk : 0);
-        p_one[k + 1] = p_one[k] + (is_short ? 0 : Tk << (lg2 - (kLgLds - lg1)));
-        p_two[k + 1] = p_two[k] + (is_short ? 0 : Tk << (lg1 - (kLgLds - lg2)));
-        p_max[k + 1] = p_max[k] + (total + kMaxChunk - 1) / kMaxChunk;
-        p_fin[k + 1] = p_fin[k] + (n[k] + kFinishChunk - 1) / kFinishChunk;
-        if (is_short) max_short = std::max(max_short, (int)n[k]);
-        else work_values += total;
-    }
-    const FidTables &tables = fid_tables();
+    std::vector<FidShape> shapes(nk);
+    for (size_t k = 0; k < nk; ++k) shapes[k] = FidShape{n_in[k], n[k], T[k]};
+    const FidPlan plan = fid_plan(shapes.data(), nk);
     Scratch mem;   // one allocation for the call's buffers
     Carver c;
-    const size_t o_jobs = c.take(nk * sizeof(FidJob)), o_pref = c.take(pref.size() * sizeof(long long));
+    const size_t o_jobs = c.take(nk * sizeof(FidJob)), o_pref = c.take(plan.pref.size() * sizeof(long long));
     const size_t o_tw = c.take(kFidStage * sizeof(FidTw)), o_hi = c.take(kFidSplit * sizeof(FidTwDD)),
                  o_lo = c.take(kFidSplit * sizeof(FidTwDD));
-    const size_t o_x = c.take((size_t)in_values * sizeof(double2)), o_work = c.take((size_t)work_values * sizeof(double2));
-    const size_t o_z = c.take((size_t)values * sizeof(double2)), o_u = c.take((size_t)points * sizeof(double)),
-                 o_v = c.take((size_t)points * sizeof(double));
-    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)p_max[nk] * sizeof(double4));
+    const size_t o_x = c.take((size_t)plan.in_values * sizeof(double2)), o_work = c.take((size_t)plan.work_values * sizeof(double2));
+    const size_t o_z = c.take((size_t)plan.values * sizeof(double2)), o_u = c.take((size_t)plan.points * sizeof(double)),
+                 o_v = c.take((size_t)plan.points * sizeof(double));
+    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)plan.items(kFidMaxPart) * sizeof(double4));
     unsigned char *base = nullptr;
     NMRFIT_HIP(mem.alloc(&base, c.total));
     FidJob *d_jobs = reinterpret_cast<FidJob *>(base + o_jobs);
     long long *d_pref = reinterpret_cast<long long *>(base + o_pref);
-    FidTw *d_tw = reinterpret_cast<FidTw *>(base + o_tw);
-    FidTwDD *d_hi = reinterpret_cast<FidTwDD *>(base + o_hi), *d_lo = reinterpret_cast<FidTwDD *>(base + o_lo);
-    double2 *d_x = reinterpret_cast<double2 *>(base + o_x), *d_work = reinterpret_cast<double2 *>(base + o_work);
-    double2 *d_z = reinterpret_cast<double2 *>(base + o_z);
-    double *d_u = reinterpret_cast<double *>(base + o_u), *d_v = reinterpret_cast<double *>(base + o_v);
-    double *d_rows = reinterpret_cast<double *>(base + o_rows);
-    double4 *d_part = reinterpret_cast<double4 *>(base + o_part);
-    std::vector<FidJob> jobs(nk);
+    const FidDeviceTables tables{reinterpret_cast<FidTw *>(base + o_tw), reinterpret_cast<FidTwDD *>(base + o_hi),
+                                 reinterpret_cast<FidTwDD *>(base + o_lo)};
+    double2 *d_x = reinterpret_cast<double2 *>(base + o_x);
+    const FidBuffers buf{reinterpret_cast<double2 *>(base + o_work), reinterpret_cast<double2 *>(base + o_z),
+                         reinterpret_cast<double *>(base + o_u),     reinterpret_cast<double *>(base + o_v),
+                         reinterpret_cast<double *>(base + o_rows),  reinterpret_cast<double4 *>(base + o_part)};
+    std::vector<const double2 *> x_of(nk);
     {
-        size_t at_x = 0, at_work = 0, at_z = 0, at_u = 0;
+        size_t at_x = 0;
         for (size_t k = 0; k < nk; ++k) {
-            const int lg = log2_exact(n[k]);
-            const bool is_short = lg <= kLgLds;
-            const size_t total = (size_t)T[k] * (size_t)n[k];
-            jobs[k] = FidJob{d_x + at_x, is_short ? nullptr : d_work + at_work, d_z + at_z, d_u + at_u, d_v + at_u,
-                             d_rows + k * kRow, d_part + p_max[k], (int32_t)n_in[k], (int32_t)n[k], T[k], lg, lg / 2, lg - lg / 2,
-                             (int32_t)(p_max[k + 1] - p_max[k])};
+            x_of[k] = d_x + at_x;
             at_x += (size_t)T[k] * (size_t)n_in[k];
-            if (!is_short) at_work += total;
-            at_z += total;
-            at_u += (size_t)n[k];
         }
     }
+    const std::vector<FidJob> jobs = fid_job_table(plan, shapes.data(), x_of.data(), buf);
     // (pageable host memory: the copies have left the host arrays when hipMemcpyAsync returns)
     NMRFIT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), nk * sizeof(FidJob), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_pref, pref.data(), pref.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_tw, tables.stage.data(), kFidStage * sizeof(FidTw), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_hi, tables.hi.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_lo, tables.lo.data(), kFidSplit * sizeof(FidTwDD), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_x, fid, (size_t)in_values * sizeof(double2), hipMemcpyHostToDevice, st));
-    const long long *d_short = d_pref, *d_one = d_short + nk + 1, *d_two = d_one + nk + 1, *d_max = d_two + nk + 1,
-                    *d_fin = d_max + nk + 1;
-    const dim3 block(kThreads);
-    const size_t block_lds = 2 * (size_t)kLdsPoints * sizeof(double);
-    if (p_short[nk]) {
-        const int plane = std::max(max_short, 16);   // (swz stays inside an aligned block of 16)
-        hipLaunchKernelGGL(fid_short_kernel, item_grid(p_short[nk]), block, 2 * (size_t)plane * sizeof(double), st, d_jobs, d_short,
-                           (int)K, plane, d_tw);
-        NMRFIT_HIP(hipGetLastError());
-    }
-    if (p_one[nk]) {
-        hipLaunchKernelGGL(fid_pass1_kernel, item_grid(p_one[nk]), block, block_lds, st, d_jobs, d_one, (int)K, d_tw, d_hi, d_lo);
-        NMRFIT_HIP(hipGetLastError());
-        hipLaunchKernelGGL(fid_pass2_kernel, item_grid(p_two[nk]), block, block_lds, st, d_jobs, d_two, (int)K, d_tw);
-        NMRFIT_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(fid_max_part_kernel, item_grid(p_max[nk]), block, 0, st, d_jobs, d_max, (int)K);
-    NMRFIT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), block, 0, st, d_jobs);
-    NMRFIT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fid_finish_kernel, item_grid(p_fin[nk]), block, 0, st, d_jobs, d_fin, (int)K);
-    NMRFIT_HIP(hipGetLastError());
-    if ((rc = staged_d2h(device, st, rows_out, d_rows, nk * kRow * sizeof(double))) != NMRFIT_OK) return rc;
-    if ((rc = staged_d2h(device, st, u_out, d_u, (size_t)points * sizeof(double))) != NMRFIT_OK) return rc;
-    if ((rc = staged_d2h(device, st, v_out, d_v, (size_t)points * sizeof(double))) != NMRFIT_OK) return rc;
-    if (transform_out) return staged_d2h(device, st, transform_out, d_z, (size_t)values * sizeof(double2));
+    NMRFIT_HIP(hipMemcpyAsync(d_pref, plan.pref.data(), plan.pref.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(fid_upload_tables(tables, st));
+    NMRFIT_HIP(hipMemcpyAsync(d_x, fid, (size_t)plan.in_values * sizeof(double2), hipMemcpyHostToDevice, st));
+    NMRFIT_HIP(fid_launch_transforms(plan, d_jobs, d_pref, tables, st));
+    NMRFIT_HIP(fid_launch_finish(plan, d_jobs, d_pref, st));
+    if ((rc = staged_d2h(device, st, rows_out, buf.rows, nk * kRow * sizeof(double))) != NMRFIT_OK) return rc;
+    if ((rc = staged_d2h(device, st, u_out, buf.u, (size_t)plan.points * sizeof(double))) != NMRFIT_OK) return rc;
+    if ((rc = staged_d2h(device, st, v_out, buf.v, (size_t)plan.points * sizeof(double))) != NMRFIT_OK) return rc;
+    if (transform_out) return staged_d2h(device, st, transform_out, buf.z, (size_t)plan.values * sizeof(double2));
     return NMRFIT_OK;
 }
 

@@ -197,12 +197,15 @@ class SynthFid:
         return N - 1 - i                       # after the reversal
 
 
-def make_fid(n, lines, T=1, seed=1, noise=0.0, offset=0.0):
+def make_fid(n, lines, T=1, seed=1, noise=0.0, offset=0.0, grpdly=None):
     """A synthetic FID: ``x_j = sum_l a_l exp(i phase_l) exp((2 pi i f_l - d_l) j)``, j = 0 .. n-1, plus complex
     Gaussian noise of standard deviation ``noise`` per part (a new draw per trace) and a constant ``offset``.
     ``lines``: tuples (f, d, a[, phase]) -- frequency in cycles per point (-0.5 <= f < 0.5 covers the spectrum),
     decay per point, amplitude, phase in radians.  Its exact DFT is a geometric series (``SynthFid.exact_dft``): a truth
-    that owes nothing to any FFT, and that says where every line must appear in the output order."""
+    that owes nothing to any FFT, and that says where every line must appear in the output order.
+    ``grpdly``: every trace of ``fid`` is delayed by that many points as a Bruker digital filter leaves it, by the inverse
+    of the ramp that nmrfit_amd.fid removes it with -- ``ifft(fft(x) * conj(rho_n))``, rho_n = ``fid.ramp(grpdly, n)``, a
+    circular shift when grpdly is an integer; ``clean`` stays the undelayed trace."""
     rng = np.random.default_rng(seed)
     lines = [tuple(ln) + (0.0,) * (4 - len(ln)) for ln in lines]
     j = np.arange(n)
@@ -212,4 +215,7 @@ def make_fid(n, lines, T=1, seed=1, noise=0.0, offset=0.0):
     fid = np.tile(clean + offset, (int(T), 1))
     if noise:
         fid = fid + noise * (rng.standard_normal((int(T), n)) + 1j * rng.standard_normal((int(T), n)))
+    if grpdly is not None:
+        from .fid import ramp
+        fid = np.fft.ifft(np.fft.fft(fid, axis=-1) * np.conj(ramp(grpdly, n)), axis=-1)
     return SynthFid(fid, clean, lines)
