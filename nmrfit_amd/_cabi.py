@@ -211,6 +211,11 @@ FID_SIGNATURES = {
 FID_COND_SIGNATURES = {
     "nmrfit_fid_condition_transform": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# FID_ANY_SIGNATURES: include/nmrfit_amd_fid_any.h (the same at any transform length: a chirp-z transform for the lengths
+# that are not powers of two)
+FID_ANY_SIGNATURES = {
+    "nmrfit_fid_transform_any": [_INT, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
 LSQ_MAX_D = 76                 # the library's limit on D = 4 + 3 P for the normal equations (NMRFIT_LSQ_MAX_D)
 WEIGHTS_MAX_POINTS = 1 << 26      # the library's limit per nmrfit_weights_build / nmrfit_batch_create_regions call
 
@@ -316,7 +321,7 @@ def lib():
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
                 + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
                 + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()) \
-                + list(FID_SIGNATURES.items()) + list(FID_COND_SIGNATURES.items()):
+                + list(FID_SIGNATURES.items()) + list(FID_COND_SIGNATURES.items()) + list(FID_ANY_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

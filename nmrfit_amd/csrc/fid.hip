@@ -370,20 +370,21 @@ FidPlan fid_plan(const FidShape *shapes, size_t nk)
     plan.K = nk;
     plan.pref.assign((size_t)kFidLaunchTables * (nk + 1), 0);
     long long *p_short = plan.pref.data(), *p_one = p_short + nk + 1, *p_two = p_one + nk + 1, *p_max = p_two + nk + 1,
-              *p_fin = p_max + nk + 1;
+              *p_fin = p_max + nk + 1, *p_max_any = p_fin + nk + 1;
     for (size_t k = 0; k < nk; ++k) {
         const int64_t n = shapes[k].n;
         const int lg = fid_log2_exact(n);
-        const bool is_short = lg <= kLgLds;
+        const bool finish_only = lg < 0, is_short = !finish_only && lg <= kLgLds, is_long = !finish_only && !is_short;
         const int lg1 = lg / 2, lg2 = lg - lg1;
-        const long long Tk = shapes[k].T, total = Tk * n;
+        const long long Tk = shapes[k].T, total = Tk * n, chunks = (total + kMaxChunk - 1) / kMaxChunk;
         p_short[k + 1] = p_short[k] + (is_short ? Tk : 0);
-        p_one[k + 1] = p_one[k] + (is_short ? 0 : Tk << (lg2 - (kLgLds - lg1)));
-        p_two[k + 1] = p_two[k] + (is_short ? 0 : Tk << (lg1 - (kLgLds - lg2)));
-        p_max[k + 1] = p_max[k] + (total + kMaxChunk - 1) / kMaxChunk;
+        p_one[k + 1] = p_one[k] + (is_long ? Tk << (lg2 - (kLgLds - lg1)) : 0);
+        p_two[k + 1] = p_two[k] + (is_long ? Tk << (lg1 - (kLgLds - lg2)) : 0);
+        p_max[k + 1] = p_max[k] + (finish_only ? 0 : chunks);
+        p_max_any[k + 1] = p_max_any[k] + (finish_only ? chunks : 0);
         p_fin[k + 1] = p_fin[k] + (n + kFinishChunk - 1) / kFinishChunk;
         if (is_short) plan.max_short = std::max(plan.max_short, (int)n);
-        else plan.work_values += total;
+        if (is_long) plan.work_values += total;
         plan.values += total;
         plan.in_values += Tk * shapes[k].n_in;
         plan.points += n;
@@ -394,18 +395,19 @@ FidPlan fid_plan(const FidShape *shapes, size_t nk)
 std::vector<FidJob> fid_job_table(const FidPlan &plan, const FidShape *shapes, const double2 *const *x_of, const FidBuffers &buf)
 {
     const size_t nk = plan.K;
-    const long long *p_max = plan.table(kFidMaxPart);
+    const long long *p_max = plan.table(kFidMaxPart), *p_max_any = plan.table(kFidMaxPartAny);
     std::vector<FidJob> jobs(nk);
     size_t at_work = 0, at_z = 0, at_u = 0;
     for (size_t k = 0; k < nk; ++k) {
-        const int lg = fid_log2_exact(shapes[k].n);
-        const bool is_short = lg <= kLgLds;
+        const int lg = fid_log2_exact(shapes[k].n);   // (-1: a finish-only job)
+        const bool is_long = lg > kLgLds;
         const size_t total = (size_t)shapes[k].T * (size_t)shapes[k].n;
-        jobs[k] = FidJob{x_of[k], is_short ? nullptr : buf.work + at_work, buf.z + at_z, buf.u ? buf.u + at_u : nullptr,
-                         buf.v ? buf.v + at_u : nullptr, buf.rows ? buf.rows + k * kRow : nullptr, buf.part ? buf.part + p_max[k] : nullptr,
-                         (int32_t)shapes[k].n_in, (int32_t)shapes[k].n, shapes[k].T, lg, lg / 2, lg - lg / 2,
-                         (int32_t)(p_max[k + 1] - p_max[k])};
-        if (!is_short) at_work += total;
+        const long long part_at = p_max[k] + p_max_any[k], part_end = p_max[k + 1] + p_max_any[k + 1];
+        jobs[k] = FidJob{x_of[k], is_long ? buf.work + at_work : nullptr, buf.z + at_z, buf.u ? buf.u + at_u : nullptr,
+                         buf.v ? buf.v + at_u : nullptr, buf.rows ? buf.rows + k * kRow : nullptr, buf.part ? buf.part + part_at : nullptr,
+                         (int32_t)shapes[k].n_in, (int32_t)shapes[k].n, shapes[k].T, lg, lg < 0 ? 0 : lg / 2, lg < 0 ? 0 : lg - lg / 2,
+                         (int32_t)(part_end - part_at)};
+        if (is_long) at_work += total;
         at_z += total;
         at_u += (size_t)shapes[k].n;
     }
@@ -454,8 +456,10 @@ hipError_t fid_launch_finish(const FidPlan &plan, const FidJob *d_jobs, const lo
     const long long *d_max = d_pref + (size_t)kFidMaxPart * (nk + 1), *d_fin = d_pref + (size_t)kFidFinish * (nk + 1);
     const dim3 block(kThreads);
     hipError_t e;
-    hipLaunchKernelGGL(fid_max_part_kernel, fid_item_grid(plan.items(kFidMaxPart)), block, 0, st, d_jobs, d_max, K);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (plan.items(kFidMaxPart)) {   // (finish-only jobs have theirs from fid_any.hip)
+        hipLaunchKernelGGL(fid_max_part_kernel, fid_item_grid(plan.items(kFidMaxPart)), block, 0, st, d_jobs, d_max, K);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), block, 0, st, d_jobs);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(fid_finish_kernel, fid_item_grid(plan.items(kFidFinish)), block, 0, st, d_jobs, d_fin, K);

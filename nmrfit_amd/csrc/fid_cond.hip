@@ -12,6 +12,7 @@
 // is not made.  Both permuted reads flip the top bit of the index and reverse the order: 64 consecutive lanes read 64
 // consecutive values (descending for the ramp stage, ascending for the store), so neither side of a stage is strided.
 // No LDS, no atomics, no scratch memory.  The ramp values are the double-double product of fid_ramp.h.
+#include "fid_any_internal.h"
 #include "fid_device.h"
 #include "fid_internal.h"
 #include "fid_ramp.h"
@@ -164,18 +165,12 @@ struct Asked {
 };
 
 }  // namespace
-}  // namespace nmrfit
 
-using namespace nmrfit;
-
-#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
-
-int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, const int64_t *n, const int32_t *T,
-                                   const double *fid, const int32_t *form, const double *g, const int32_t *window_of, int32_t M,
-                                   const int64_t *window_len, const double *windows, double *u_out, double *v_out,
-                                   double *rows_out, double *transform_out, double *conditioned_out)
+int fid_condition_transform_run(const std::string &who, bool any_length, int device, int32_t K, const int64_t *n_in, const int64_t *n,
+                                const int32_t *T, const double *fid, const int32_t *form, const double *g, const int32_t *window_of,
+                                int32_t M, const int64_t *window_len, const double *windows, double *u_out, double *v_out,
+                                double *rows_out, double *transform_out, double *conditioned_out)
 {
-    const std::string who = "nmrfit_fid_condition_transform";
     if (K <= 0 || !n_in || !n || !T || !fid || !form || !g || !window_of || !u_out || !v_out || !rows_out)
         return refuse(NMRFIT_E_INVALID, who + ": the number of spectra must be > 0 and n_in, n, T, fid, form, g, window_of, u_out, "
                                               "v_out, rows_out non-null");
@@ -223,18 +218,37 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
                 return refuse(NMRFIT_E_INVALID, who + ": a window value is not finite (window " + std::to_string(m) + ")");
     const int64_t max_values = (int64_t)1 << 26;
     int64_t values = 0;
+    std::vector<FidAnyAsk> asks;   // the spectra on the chirp path (any_length alone)
+    std::vector<size_t> of_any;
     for (int32_t k = 0; k < K; ++k) {
         const int lg = fid_log2_exact(n[k]);
-        if (lg < 1 || lg > kLgMax)
+        const std::string at = " (spectrum " + std::to_string(k) + ")";
+        if (any_length && lg < 0) {
+            if (n[k] < kFidAnyMin || n[k] > kFidAnyMax)
+                return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
+                                                        ", or any other length, 3 .. 2^21 - 1" + at);
+            if (asked[k].form == NMRFIT_FID_FORM_SPECTRUM)
+                return refuse(NMRFIT_E_UNSUPPORTED, who + ": form 2 (spectrum) needs a transform length that is a power of two" + at +
+                                                        ": its ramp tables are split at 2^11; use form 1 (fid), or zero fill");
+            asks.push_back(FidAnyAsk{n[k], asked[k].n_out, T[k]});
+            of_any.push_back((size_t)k);
+        } else if (lg < 1 || lg > kLgMax) {
+            if (any_length)
+                return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
+                                                        ", or any other length, 3 .. 2^21 - 1" + at);
             return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
                                                     " (spectrum " + std::to_string(k) + "): zero fill to the next power of two");
+        }
         if (values <= max_values)   // (each term < 2^54: the sum cannot overflow)
             values += (int64_t)T[k] * n[k] + (asked[k].form == NMRFIT_FID_FORM_FID ? (int64_t)T[k] * n_in[k] : 0);
     }
-    if (K > kWeightsMaxSpectra || values > max_values)
+    const bool too_many = K > kWeightsMaxSpectra || values > max_values;
+    if (!too_many && !asks.empty()) values += fid_any_values(asks.data(), asks.size());   // (K < 2^16 terms < 2^54)
+    if (too_many || values > max_values)
         return refuse(NMRFIT_E_UNSUPPORTED, who + ": a call takes at most " + std::to_string(kWeightsMaxSpectra) + " spectra and " +
                                                 std::to_string(max_values) + " transformed values (T n summed over the spectra, "
-                                                "plus T n_in of those in form 1)");
+                                                "plus T n_in of those in form 1" +
+                                                (any_length ? ", plus 2 T M of those whose n is no power of two and 2 M per distinct such n)" : ")"));
     int rc = use_device(device);
     if (rc != NMRFIT_OK) return rc;
     StreamLease lease(device);
@@ -253,6 +267,8 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
     }
     const size_t nk1 = of1.size();
     const FidPlan plan = fid_plan(shapes.data(), nk), plan1 = fid_plan(shapes1.data(), nk1);
+    FidAnyStage any;
+    any.plan(asks);
     std::vector<long long> cpref((size_t)kCondTables * (nk + 1), 0);
     long long *p_ramp = cpref.data(), *p_store = p_ramp + nk + 1, *p_win = p_store + nk + 1, *p_spec = p_win + nk + 1;
     int64_t raw_values = 0, cond_values = 0;
@@ -303,7 +319,8 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
     const size_t o_cond = c.take((size_t)cond_values * sizeof(double2));
     const size_t o_work = c.take((size_t)plan.work_values * sizeof(double2)), o_z = c.take((size_t)plan.values * sizeof(double2));
     const size_t o_u = c.take((size_t)plan.points * sizeof(double)), o_v = c.take((size_t)plan.points * sizeof(double));
-    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)plan.items(kFidMaxPart) * sizeof(double4));
+    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)plan.parts() * sizeof(double4));
+    any.carve(c);
     unsigned char *base = nullptr;
     NMRFIT_HIP(mem.alloc(&base, c.total));
     FidJob *d_jobs = reinterpret_cast<FidJob *>(base + o_jobs), *d_jobs_a = reinterpret_cast<FidJob *>(base + o_jobs_a),
@@ -377,8 +394,17 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
     }
     if (!ramps.empty()) NMRFIT_HIP(hipMemcpyAsync(d_ramps, ramps.data(), ramps.size() * sizeof(FidTwDD), hipMemcpyHostToDevice, st));
     if (window_at[M]) NMRFIT_HIP(hipMemcpyAsync(d_win, windows, window_at[M] * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!asks.empty()) {
+        std::vector<const double2 *> x_any(asks.size());
+        std::vector<double2 *> z_any(asks.size());
+        for (size_t i = 0; i < asks.size(); ++i) {
+            x_any[i] = x_main[of_any[i]];
+            z_any[i] = jobs[of_any[i]].z;
+        }
+        NMRFIT_HIP(any.upload(base, x_any.data(), z_any.data(), st));
+    }
 
-    // ---- the launches: at most 16
+    // ---- the launches: at most 16, at most 27 with spectra on the chirp path
     const long long *d_ramp = d_cpref, *d_store = d_ramp + nk + 1, *d_window = d_store + nk + 1, *d_spec = d_window + nk + 1;
     const dim3 block(kThreads);
     if (p_ramp[nk]) {
@@ -394,6 +420,7 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
         NMRFIT_HIP(hipGetLastError());
     }
     NMRFIT_HIP(fid_launch_transforms(plan, d_jobs, d_pref, tables, st));
+    NMRFIT_HIP(any.launch(tables, plan, d_jobs, d_pref, st));
     if (p_spec[nk]) {
         hipLaunchKernelGGL(fidc_spectrum_kernel, fid_item_grid(p_spec[nk]), block, 0, st, d_cjobs, d_spec, (int)K);
         NMRFIT_HIP(hipGetLastError());
@@ -427,6 +454,21 @@ int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, c
         }
     }
     return NMRFIT_OK;
+}
+
+}  // namespace nmrfit
+
+using namespace nmrfit;
+
+#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
+
+int nmrfit_fid_condition_transform(int device, int32_t K, const int64_t *n_in, const int64_t *n, const int32_t *T,
+                                   const double *fid, const int32_t *form, const double *g, const int32_t *window_of, int32_t M,
+                                   const int64_t *window_len, const double *windows, double *u_out, double *v_out,
+                                   double *rows_out, double *transform_out, double *conditioned_out)
+{
+    return fid_condition_transform_run("nmrfit_fid_condition_transform", false, device, K, n_in, n, T, fid, form, g, window_of, M,
+                                       window_len, windows, u_out, v_out, rows_out, transform_out, conditioned_out);
 }
 
 #pragma GCC visibility pop

@@ -43,6 +43,18 @@ rho_n(i) = exp(+2 pi i g i / n):
     window_em / window_gauss / window_sine                 plain numpy windows, ``first_point=`` for W[0]
 
 Only a group delay given as a number (GRPDLY) is taken; the DSPFVS / DECIM table of old firmware is out of scope.
+
+ANY LENGTH (include/nmrfit_amd_fid_any.h, csrc/fid_any.hip).  ``core.load`` transforms a FID at the length it has; the
+kernels take powers of two.  With ``any_length=True``, ``transform_many`` and ``spectra_from_fids`` transform a length that
+is not a power of two (3 .. 2^21 - 1) at exactly that length, by a chirp-z (Bluestein) transform on the device
+(nmrfit_fid_transform_any): three transforms of length M = 2^m >= 2 N - 1 by the same kernels and four element-wise stages.
+``grpdly_mode="fid"`` then needs no ``zero_fill``: a Bruker FID of s = 2^m points comes out on the grid of s - floor(g + 2)
+points, as ``core.load`` makes it.  ``grpdly_mode="spectrum"`` still needs a power of two.  Without ``any_length`` every
+call, message and bit is as before.
+
+    bluestein_host(x, N)                     the header's definition step by step in numpy, centred: fp64 (the mirror), or
+                                             long double for a clongdouble input (the tests' truth)
+    chirp(N)                                 c[k] = exp(-i pi k^2 / N), the angle reduced mod 2 N exactly in integers
 """
 import functools
 
@@ -54,6 +66,7 @@ ROW = 6                  # doubles per row (NMRFIT_FID_ROW): status, Re m, Im m,
 MAX_LOG2 = 22            # NMRFIT_FID_MAX_LOG2
 LDS_LOG2 = 12            # NMRFIT_FID_LDS_LOG2: the longest transform that is one LDS-resident block
 MAX_VALUES = 1 << 26     # T n summed over the spectra of one library call
+ANY_MIN, ANY_MAX = 3, (1 << 21) - 1      # NMRFIT_FID_ANY_MIN / _MAX: the lengths the chirp path takes (no power of two)
 OK, ZERO, NOT_FINITE = 0, 1, 2
 FORM_NONE, FORM_FID, FORM_SPECTRUM = 0, 1, 2      # NMRFIT_FID_FORM_*
 _MODES = {"fid": FORM_FID, "spectrum": FORM_SPECTRUM}
@@ -79,9 +92,14 @@ def _as_traces(fid, keep_long=False):
     return np.ascontiguousarray(a.reshape(-1, a.shape[-1]), dtype=np.complex128)
 
 
-def transform_length(n_in, zero_fill=None):
+def _is_pow2(n):
+    return n >= 1 and not n & (n - 1)
+
+
+def transform_length(n_in, zero_fill=None, any_length=False):
     """The transform length of a trace of n_in points: n_in itself (None), the next power of two ("pow2"), or the int
-    given.  ValueError, naming ``zero_fill``, for a length the device refuses."""
+    given.  ValueError, naming ``zero_fill``, for a length the device refuses: anything but a power of two, 2 .. 2^22 --
+    or, with ``any_length``, any other length, 3 .. 2^21 - 1."""
     if zero_fill is None:
         n = int(n_in)
     elif isinstance(zero_fill, str):
@@ -94,6 +112,11 @@ def transform_length(n_in, zero_fill=None):
         n = int(zero_fill)
         if n < n_in:
             raise ValueError("fid: zero_fill=%d is shorter than the trace (%d points)" % (n, n_in))
+    if any_length and not _is_pow2(n):
+        if n < ANY_MIN or n > ANY_MAX:
+            raise ValueError("fid: a transform length is a power of two, 2 .. 2^%d, or with any_length any other length, "
+                             "%d .. 2^21 - 1 (got %d): pass a zero_fill within these" % (MAX_LOG2, ANY_MIN, n))
+        return n
     if n < 2 or n & (n - 1) or n > 1 << MAX_LOG2:
         raise ValueError("fid: a transform length is a power of two, 2 .. 2^%d (got %d): pass zero_fill='pow2', or "
                          "zero_fill=<a power of two>; other lengths are refused, not emulated" % (MAX_LOG2, n))
@@ -256,6 +279,91 @@ def condition_host(fid, grpdly=None, mode="fid", window=None, zero_fill=None):
     return xc, Y
 
 
+# -- any length: the numpy restatement ------------------------------------------------------------------------------
+
+def conv_length(N):
+    """M = 2^m, the smallest power of two >= 2 N - 1."""
+    M = 1
+    while M < 2 * int(N) - 1:
+        M *= 2
+    return M
+
+
+@functools.lru_cache(maxsize=16)
+def _chirp_cached(N, long):
+    k = np.arange(N, dtype=np.int64)
+    r = (k * k) % (2 * N)                                        # exact: k^2 < 2^42
+    eighths = 4 * r                                              # 4 r / N = oct + rem / N
+    octant = eighths // N
+    rem = eighths - octant * N
+    odd = (octant & 1).astype(bool)
+    rr = np.where(odd, N - rem, rem).astype(np.longdouble)
+    pi = np.arctan2(np.longdouble(0), np.longdouble(-1))
+    th = rr / np.longdouble(N) * (pi / np.longdouble(4))
+    cc, ss = np.cos(th), np.sin(th)
+    half = np.sqrt(np.longdouble(0.5))
+    exact = rem == 0                                             # a multiple of an eighth of a turn
+    cc = np.where(exact, np.where(odd, half, np.longdouble(1)), cc)
+    ss = np.where(exact, np.where(odd, half, np.longdouble(0)), ss)
+    cc, ss = np.where(odd & ~exact, ss, cc), np.where(odd & ~exact, cc, ss)
+    quarter = octant >> 1
+    C = np.select([quarter == 0, quarter == 1, quarter == 2], [cc, -ss, -cc], ss)
+    S = np.select([quarter == 0, quarter == 1, quarter == 2], [ss, cc, -ss], -cc)
+    c = (C - 1j * S).astype(np.clongdouble)                      # the negative angle
+    c = c if long else c.astype(np.complex128)
+    c.setflags(write=False)
+    return c
+
+
+def chirp(N, dtype=np.complex128):
+    """c[k] = exp(-i pi k^2 / N), k = 0 .. N-1, as csrc/fid_chirp.h makes it: k^2 reduced mod 2 N exactly, folded to an
+    octant, cos and sin in long double; fp64 is the rounding of that.  Read-only (cached)."""
+    return _chirp_cached(int(N), np.dtype(dtype) == np.clongdouble)
+
+
+def _times(a, b):
+    """The complex product by its parts, each rounded once: (a c - b d, a d + b c)."""
+    out = np.empty(np.broadcast(a, b).shape, dtype=np.result_type(a, b))
+    out.real = a.real * b.real - a.imag * b.imag
+    out.imag = a.real * b.imag + a.imag * b.real
+    return out
+
+
+def bluestein_host(x, N):
+    """include/nmrfit_amd_fid_any.h's definition step by step in numpy: Y (T, N) = fftshift(fft(x, N)) of every trace of x
+    (n_in' <= N points) by the chirp-z transform -- a = x' c zero filled to M, b the wrapped conj(c), P = fft(a) fft(b),
+    p = fft(P)[(-j) mod M] / M, X = p c, Y[i] = X[(i + N - N // 2) mod N].  fp64 for a complex128 input (the mirror of the
+    device's steps; np.fft's transforms are not the device's bit for bit), long double for a clongdouble one (the truth)."""
+    x = _as_traces(x, keep_long=True)
+    long = x.dtype == np.clongdouble
+    real = np.longdouble if long else np.float64
+    N, n_in = int(N), x.shape[-1]
+    if N < 1 or n_in > N:
+        raise ValueError("fid: bluestein_host needs N >= the trace's length (%d, got N = %d)" % (n_in, N))
+    c = chirp(N, x.dtype)
+    M = conv_length(N)
+    a = np.zeros((x.shape[0], M), dtype=x.dtype)
+    a[:, :n_in] = _times(x, c[:n_in])
+    b = np.zeros(M, dtype=x.dtype)
+    b[:N] = np.conj(c)
+    b[M - np.arange(1, N)] = np.conj(c[1:])
+    P = _times(np.fft.fft(a, axis=-1), np.fft.fft(b))
+    p = np.fft.fft(P, axis=-1)[:, (-np.arange(M)) % M] / real(M)          # the inverse transform by the forward one
+    X = _times(p[:, :N], c)
+    return X[:, (np.arange(N) + N - N // 2) % N]
+
+
+def filter_peak(N):
+    """beta = max_k |B[k]| of the definition, B = fft_M(b), in long double (a property of the definition, for the error
+    bound of the header)."""
+    c = chirp(N, np.clongdouble)
+    M = conv_length(N)
+    b = np.zeros(M, dtype=np.clongdouble)
+    b[:N] = np.conj(c)
+    b[M - np.arange(1, N)] = np.conj(c[1:])
+    return float(np.abs(np.fft.fft(b)).max())
+
+
 def _first_point(W, first_point):
     W[0] = W[0] * first_point
     return W
@@ -281,13 +389,19 @@ def window_sine(n, off=0.0, end=1.0, power=1.0, first_point=1.0):
 
 # -- the device call -----------------------------------------------------------------------------------------------
 
-def _calls(values):
-    """(first, last + 1) of consecutive spectra per library call: at most 65535 spectra and MAX_VALUES values."""
-    out, i0, acc = [], 0, 0
+def _calls(values, shared=None):
+    """(first, last + 1) of consecutive spectra per library call: at most 65535 spectra and MAX_VALUES values.
+    ``shared``: per spectrum None or (key, values) -- values counted once per distinct key of a call (the chirp path's
+    filter planes, once per distinct N)."""
+    out, i0, acc, keys = [], 0, 0, set()
     for i, val in enumerate(values):
-        if i > i0 and (acc + val > MAX_VALUES or i - i0 == _cabi._MAX_SPECTRA_PER_CALL):
+        key, extra = shared[i] if shared is not None and shared[i] is not None else (None, 0)
+        if i > i0 and (acc + val + (0 if key in keys else extra) > MAX_VALUES or i - i0 == _cabi._MAX_SPECTRA_PER_CALL):
             out.append((i0, i))
-            i0, acc = i, 0
+            i0, acc, keys = i, 0, set()
+        if key is not None and key not in keys:
+            keys.add(key)
+            acc += extra
         acc += val
     if len(values):
         out.append((i0, len(values)))
@@ -346,7 +460,7 @@ def _conditioning(xs, grpdly, grpdly_mode, window, truncate_grpdly):
 
 
 def transform_many(fids, zero_fill=None, device=0, return_transform=False, grpdly=None, grpdly_mode="fid", window=None,
-                   truncate_grpdly=True, return_conditioned=False):
+                   truncate_grpdly=True, return_conditioned=False, any_length=False):
     """The spectra of K FIDs on the GPU (nmrfit_fid_transform).  Each FID is a complex64 or complex128 array of shape
     (n,) or (T, n): T traces that are summed after the normalisation, as ``core.load`` does.  ``zero_fill``: None (the
     transform length is the trace's), "pow2" (the next power of two) or an int; the zeros are made on the device.
@@ -364,23 +478,38 @@ def transform_many(fids, zero_fill=None, device=0, return_transform=False, grpdl
     of the two per FID.
     ``window``: None, n_in' reals (``window_em`` and the others; ``conditioned_length`` gives n_in'), or one per FID; equal
     windows are uploaded once.  ``return_conditioned``: the traces as they enter the main transform, (T, n_in'), last in
-    the tuple.  With all of these left alone the call is the one made before they existed."""
+    the tuple.  With all of these left alone the call is the one made before they existed.
+
+    ``any_length=True``: a transform length that is not a power of two (3 .. 2^21 - 1) is transformed at exactly that
+    length on the device (nmrfit_fid_transform_any; the module docstring); ``grpdly_mode="fid"`` then needs no
+    ``zero_fill``.  "spectrum" with such a length stays refused.  A call's values then count 2 T M per such FID and 2 M per
+    distinct such length as well (M = ``conv_length(n)``).  Powers of two go the way they went, with the same bits."""
     xs = [_as_traces(f) for f in fids]
     plain = grpdly is None and window is None and not return_conditioned
     if plain:
         conds, windows = [(FORM_NONE, 0.0, x.shape[1], -1) for x in xs], []
     else:
         conds, windows = _conditioning(xs, grpdly, grpdly_mode, window, truncate_grpdly)
-    ns = [transform_length(c[2], zero_fill) for c in conds]
-    values = [x.shape[0] * (n + (x.shape[1] if c[0] == FORM_FID else 0)) for x, n, c in zip(xs, ns, conds)]
+    ns = [transform_length(c[2], zero_fill, any_length) for c in conds]
+    chirped = [not _is_pow2(n) for n in ns]                      # (any_length alone lets such a length through)
+    for k, c in enumerate(conds):
+        if chirped[k] and c[0] == FORM_SPECTRUM:
+            raise ValueError("fid: grpdly_mode='spectrum' needs a transform length that is a power of two (FID %d: %d): pass "
+                             "zero_fill, or grpdly_mode='fid'" % (k, ns[k]))
+    values = [x.shape[0] * (n + (x.shape[1] if c[0] == FORM_FID else 0) + (2 * conv_length(n) if ch else 0))
+              for x, n, c, ch in zip(xs, ns, conds, chirped)]
+    shared = [(n, 2 * conv_length(n)) if ch else None for n, ch in zip(ns, chirped)]
     for k, val in enumerate(values):
+        if shared[k] is not None:
+            val += shared[k][1]
         if val > MAX_VALUES:
             raise ValueError("fid: T n = %d exceeds %d values per call (FID %d): a smaller zero_fill, or fewer traces"
                              % (val, MAX_VALUES, k))
     lib = _cabi.lib() if xs else None
     result = []
-    for i0, i1 in _calls(values):
+    for i0, i1 in _calls(values, shared):
         sel = range(i0, i1)
+        by_chirp = any(chirped[k] for k in sel)
         K = len(sel)
         n_in = np.array([xs[k].shape[1] for k in sel], dtype=np.int64)
         n = np.array([ns[k] for k in sel], dtype=np.int64)
@@ -389,10 +518,11 @@ def transform_many(fids, zero_fill=None, device=0, return_transform=False, grpdl
         u, v = np.empty(int(n.sum())), np.empty(int(n.sum()))
         rows = np.empty(K * ROW)
         Z = np.empty(2 * int((T * n).sum())) if return_transform else None
-        if plain:
+        if plain and not by_chirp:
             _cabi.check(lib.nmrfit_fid_transform(int(device), K, _cabi.ptr(n_in), _cabi.ptr(n), _cabi.ptr(T), _cabi.ptr(flat),
                                                  _cabi.ptr(u), _cabi.ptr(v), _cabi.ptr(rows), _cabi.ptr(Z)))
         else:
+            call = lib.nmrfit_fid_transform_any if by_chirp else lib.nmrfit_fid_condition_transform
             form = np.array([conds[k][0] for k in sel], dtype=np.int32)
             g = np.array([conds[k][1] for k in sel], dtype=np.float64)
             n_out = np.array([conds[k][2] for k in sel], dtype=np.int64)
@@ -401,7 +531,7 @@ def transform_many(fids, zero_fill=None, device=0, return_transform=False, grpdl
             window_len = np.array([len(windows[m]) for m in used], dtype=np.int64)
             wflat = np.concatenate([windows[m] for m in used]) if used else None
             C = np.empty(2 * int((T * n_out).sum())) if return_conditioned else None
-            _cabi.check(lib.nmrfit_fid_condition_transform(
+            _cabi.check(call(
                 int(device), K, _cabi.ptr(n_in), _cabi.ptr(n), _cabi.ptr(T), _cabi.ptr(flat), _cabi.ptr(form), _cabi.ptr(g),
                 _cabi.ptr(window_of), len(used), _cabi.ptr(window_len) if used else None, _cabi.ptr(wflat), _cabi.ptr(u),
                 _cabi.ptr(v), _cabi.ptr(rows), _cabi.ptr(Z), _cabi.ptr(C)))
@@ -422,11 +552,12 @@ def transform_many(fids, zero_fill=None, device=0, return_transform=False, grpdl
 
 
 def spectra_from_fids(fids, sw, sfrq, tof, zero_fill=None, device=0, grpdly=None, grpdly_mode="fid", window=None,
-                      truncate_grpdly=True):
+                      truncate_grpdly=True, any_length=False):
     """``core.load`` without the file reader, for many FIDs at once: a list of ``Data(w, u, v)`` with (u, v) from
     ``transform_many`` and ``w = ppm_axis(n, sw, sfrq, tof)``, ready for ``shift_phase_many`` / ``select_peaks_many`` /
     ``fit_many``.  ``sw``, ``sfrq``, ``tof`` (Hz, MHz, Hz): scalars or one value per FID.  ``grpdly``, ``grpdly_mode``,
-    ``window``, ``truncate_grpdly``: the conditioning of ``transform_many`` (a Bruker FID: ``grpdly=<GRPDLY>``).  A FID whose
+    ``window``, ``truncate_grpdly``: the conditioning of ``transform_many`` (a Bruker FID: ``grpdly=<GRPDLY>``); ``any_length``:
+    its exact-length transform (the grid ``core.load`` makes: no ``zero_fill`` needed).  A FID whose
     transform is not finite, or that is all zero, raises ValueError (nothing is returned)."""
     from .containers import Data
 
@@ -440,7 +571,7 @@ def spectra_from_fids(fids, sw, sfrq, tof, zero_fill=None, device=0, grpdly=None
     K = len(fids)
     sws, sfrqs, tofs = (per_spectrum(x, K, name) for x, name in ((sw, "sw"), (sfrq, "sfrq"), (tof, "tof")))
     got = transform_many(fids, zero_fill=zero_fill, device=device, grpdly=grpdly, grpdly_mode=grpdly_mode, window=window,
-                         truncate_grpdly=truncate_grpdly)
+                         truncate_grpdly=truncate_grpdly, any_length=any_length)
     for k, (_, _, row) in enumerate(got):
         if row[0] != OK:
             raise ValueError("spectra_from_fids: FID %d %s" % (k, "is all zero" if row[0] == ZERO else "has a transform that is not finite"))
