@@ -55,7 +55,9 @@
  *     || Y^ - Y ||_2 <= ( beta (2 eps + 2 kappa + sqrt(2) gamma_2) + (eps + mu) sqrt(n_in' (2 N - 1)) ) ||x'||_2
  * An error of the conditioned trace (form 1, the window: nmrfit_amd_fid_cond.h's || x'^ - x' ||_2) passes through the
  * same linear map and is carried by beta: + beta || x'^ - x' ||_2.  The max|A| ||dB||_2 term takes every error of B to
- * meet the largest value of A: it is pessimistic by about sqrt(N).
+ * meet the largest value of A: it is pessimistic by about sqrt(N).  The derivation uses n_in' only through
+ * max|A| <= ||a||_1 <= sqrt(n_in') ||x'||_2: for a trace with s non-zero points ||a||_1 <= sqrt(s) ||x'||_2, so the bound
+ * holds with s in place of n_in' (tests/fid_lengths_support.py: sparse_bar).
  *
  * PURITY.  As nmrfit_amd_fid_cond.h: no atomics; no dependence on K, on the position in the batch, on which other jobs
  * share an N, a ramp or a window, or on what device memory held before the call.

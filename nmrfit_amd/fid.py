@@ -353,9 +353,10 @@ def bluestein_host(x, N):
     return X[:, (np.arange(N) + N - N // 2) % N]
 
 
+@functools.lru_cache(maxsize=64)
 def filter_peak(N):
     """beta = max_k |B[k]| of the definition, B = fft_M(b), in long double (a property of the definition, for the error
-    bound of the header)."""
+    bound of the header).  Cached: a transform of M points in long double per distinct N."""
     c = chirp(N, np.clongdouble)
     M = conv_length(N)
     b = np.zeros(M, dtype=np.clongdouble)
