@@ -6,12 +6,13 @@
 //   fid_pass1_kernel      n = n1 n2 > 4096: a workgroup takes 4096 / n1 adjacent columns (stride n2) of one trace,
 //                         transforms them in LDS and stores them times the twiddle omega_n^(j2 q1)
 //   fid_pass2_kernel      ... and 4096 / n2 adjacent rows (n2 contiguous points each), whose store centres and reverses
-//   fid_max_part_kernel   the lexicographic maximum and a not-finite flag of 8192 values of a spectrum
+//   fid_max_part_kernel   the lexicographic maximum and a not-finite flag of 8192 values of a spectrum, of any length
 //   fid_max_kernel        ... of the partial maxima of a spectrum: the row
 //   fid_finish_kernel     1024 output points of a spectrum: the quotient of every trace's value, summed over the traces
 // Every launch is a flat list of work items over all spectra of the call; a workgroup finds its spectrum by a binary
 // search in the launch's prefix table (K + 1 numbers): at most six launches whatever K and T.  No atomics, no scratch
-// memory; every value is a pure function of the spectrum's own input (the definition's PURITY).
+// memory; every value is a pure function of the spectrum's own input (the definition's PURITY).  The entry points and
+// the body of a call are fid_call.hip's; this file exports nothing.
 //
 // THE LDS BLOCK.  Up to 4096 complex points as two planes of doubles (re, im).  C = 2^lgC transforms of length L are
 // interleaved, point p of transform c at index p C + c, so a stage of C > 1 transforms is a stage of one transform of
@@ -32,11 +33,9 @@
 #include "fid_device.h"
 #include "fid_internal.h"
 #include "nmrfit_amd_fid.h"
-#include "weights_internal.h"
 
 #include <climits>
 #include <cmath>
-#include <string>
 #include <vector>
 
 namespace nmrfit {
@@ -135,11 +134,10 @@ __global__ __launch_bounds__(kThreads) void fid_short_kernel(const FidJob *__res
 {
     extern __shared__ __align__(16) double lds[];
     double *re = lds, *im = lds + plane;
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const long long t = item - pref[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const FidJob &q = jobs[at.k];
+    const long long t = at.local();
     const int n = q.n, n_in = q.n_in;
     const double2 *__restrict__ x = q.x + t * n_in;
     for (int e = threadIdx.x; e < n; e += kThreads) {
@@ -163,11 +161,10 @@ __global__ __launch_bounds__(kThreads) void fid_pass1_kernel(const FidJob *__res
 {
     extern __shared__ __align__(16) double lds[];
     double *re = lds, *im = lds + kLdsPoints;
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const long long local = item - pref[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const FidJob &q = jobs[at.k];
+    const long long local = at.local();
     const int lg1 = q.lg1, lg2 = q.lg2, lgC = kLgLds - lg1, n2 = 1 << lg2, n_in = q.n_in;
     const long long t = local >> (lg2 - lgC);                        // n2 / C groups of columns per trace
     const int col0 = (int)(local & ((1 << (lg2 - lgC)) - 1)) << lgC;   // the group's first column
@@ -198,11 +195,10 @@ __global__ __launch_bounds__(kThreads) void fid_pass2_kernel(const FidJob *__res
 {
     extern __shared__ __align__(16) double lds[];
     double *re = lds, *im = lds + kLdsPoints;
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const long long local = item - pref[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const FidJob &q = jobs[at.k];
+    const long long local = at.local();
     const int lg1 = q.lg1, lg2 = q.lg2, lgR = kLgLds - lg2, n = q.n;
     const long long t = local >> (lg1 - lgR);                        // n1 / R groups of rows per trace
     const int row0 = (int)(local & ((1 << (lg1 - lgR)) - 1)) << lgR;   // the group's first row
@@ -259,20 +255,30 @@ __global__ __launch_bounds__(kThreads) void fid_max_part_kernel(const FidJob *__
                                                                 int K)
 {
     __shared__ Best s_best[kWaves];
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const int chunk = (int)(item - pref[k]), n = q.n;
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const FidJob &q = jobs[at.k];
+    const int chunk = (int)at.local(), n = q.n;
     const long long total = (long long)q.T * n, from = (long long)chunk * kMaxChunk;
     const long long to = from + kMaxChunk < total ? from + kMaxChunk : total;
     const double2 *__restrict__ z = q.z;
     Best mine = best_init();
-    for (long long p = from + threadIdx.x; p < to; p += kThreads) {
-        const double2 val = z[p];
-        const long long j = p & (n - 1);
-        // (Z[t n + j] is Y[t n + n - 1 - j])
-        best_take(mine, val.x, val.y, p + (n - 1) - 2 * j, !(isfinite(val.x) && isfinite(val.y)));
+    // (Z[t n + j] is Y[t n + n - 1 - j]; the branch is the workgroup's: one job)
+    if (q.lg >= 0) {   // n is a power of two: the point within the trace by a mask
+        for (long long p = from + threadIdx.x; p < to; p += kThreads) {
+            const double2 val = z[p];
+            const long long j = p & (n - 1);
+            best_take(mine, val.x, val.y, p + (n - 1) - 2 * j, !(isfinite(val.x) && isfinite(val.y)));
+        }
+    } else {   // a finish-only job, n any length: by a remainder (one 64-bit division per item, a 32-bit one per value)
+        const unsigned un = (unsigned)n;
+        const long long t0 = from / un;
+        const unsigned j0 = (unsigned)(from - t0 * un);
+        for (long long p = from + threadIdx.x; p < to; p += kThreads) {
+            const double2 val = z[p];
+            const unsigned at = j0 + (unsigned)(p - from), dt = at / un, j = at - dt * un;   // (at < n + 8192 < 2^32)
+            best_take(mine, val.x, val.y, (t0 + dt) * (long long)un + (un - 1 - j), !(isfinite(val.x) && isfinite(val.y)));
+        }
     }
     const Best all = best_of_workgroup(mine, s_best);
     if (threadIdx.x == 0) q.part[chunk] = make_double4(all.re, all.im, all.bad ? 0.0 : (double)all.idx, all.bad ? 1.0 : 0.0);
@@ -303,11 +309,10 @@ __global__ __launch_bounds__(kThreads) void fid_max_kernel(const FidJob *__restr
 __global__ __launch_bounds__(kThreads) void fid_finish_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref,
                                                               int K)
 {
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const int n = q.n, T = q.T, from = (int)(item - pref[k]) * kFinishChunk;
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const FidJob &q = jobs[at.k];
+    const int n = q.n, T = q.T, from = (int)at.local() * kFinishChunk;
     const double status = q.row[0], mr = q.row[1], mi = q.row[2];
     const bool first = fabs(mr) >= fabs(mi);
     const double rat = first ? mi / mr : mr / mi;
@@ -345,7 +350,6 @@ const FidTables &fid_tables()
     return t;
 }
 
-
 }  // namespace
 
 // ---- the pieces of a call (fid_internal.h) --------------------------------------------------------------------------
@@ -367,22 +371,18 @@ int fid_log2_exact(int64_t n)
 FidPlan fid_plan(const FidShape *shapes, size_t nk)
 {
     FidPlan plan;
-    plan.K = nk;
-    plan.pref.assign((size_t)kFidLaunchTables * (nk + 1), 0);
-    long long *p_short = plan.pref.data(), *p_one = p_short + nk + 1, *p_two = p_one + nk + 1, *p_max = p_two + nk + 1,
-              *p_fin = p_max + nk + 1, *p_max_any = p_fin + nk + 1;
+    plan.tab = ItemTables(kFidLaunchTables, nk);
     for (size_t k = 0; k < nk; ++k) {
         const int64_t n = shapes[k].n;
-        const int lg = fid_log2_exact(n);
-        const bool finish_only = lg < 0, is_short = !finish_only && lg <= kLgLds, is_long = !finish_only && !is_short;
+        const int lg = fid_log2_exact(n);   // (-1: a finish-only job)
+        const bool is_short = lg >= 0 && lg <= kLgLds, is_long = lg > kLgLds;
         const int lg1 = lg / 2, lg2 = lg - lg1;
-        const long long Tk = shapes[k].T, total = Tk * n, chunks = (total + kMaxChunk - 1) / kMaxChunk;
-        p_short[k + 1] = p_short[k] + (is_short ? Tk : 0);
-        p_one[k + 1] = p_one[k] + (is_long ? Tk << (lg2 - (kLgLds - lg1)) : 0);
-        p_two[k + 1] = p_two[k] + (is_long ? Tk << (lg1 - (kLgLds - lg2)) : 0);
-        p_max[k + 1] = p_max[k] + (finish_only ? 0 : chunks);
-        p_max_any[k + 1] = p_max_any[k] + (finish_only ? chunks : 0);
-        p_fin[k + 1] = p_fin[k] + (n + kFinishChunk - 1) / kFinishChunk;
+        const long long Tk = shapes[k].T, total = Tk * n;
+        plan.tab.add(kFidShort, k, is_short ? Tk : 0);
+        plan.tab.add(kFidPass1, k, is_long ? Tk << (lg2 - (kLgLds - lg1)) : 0);
+        plan.tab.add(kFidPass2, k, is_long ? Tk << (lg1 - (kLgLds - lg2)) : 0);
+        plan.tab.add(kFidMaxPart, k, (total + kMaxChunk - 1) / kMaxChunk);
+        plan.tab.add(kFidFinish, k, (n + kFinishChunk - 1) / kFinishChunk);
         if (is_short) plan.max_short = std::max(plan.max_short, (int)n);
         if (is_long) plan.work_values += total;
         plan.values += total;
@@ -394,19 +394,18 @@ FidPlan fid_plan(const FidShape *shapes, size_t nk)
 
 std::vector<FidJob> fid_job_table(const FidPlan &plan, const FidShape *shapes, const double2 *const *x_of, const FidBuffers &buf)
 {
-    const size_t nk = plan.K;
-    const long long *p_max = plan.table(kFidMaxPart), *p_max_any = plan.table(kFidMaxPartAny);
+    const size_t nk = plan.tab.K;
+    const long long *p_max = plan.tab.row(kFidMaxPart);
     std::vector<FidJob> jobs(nk);
     size_t at_work = 0, at_z = 0, at_u = 0;
     for (size_t k = 0; k < nk; ++k) {
         const int lg = fid_log2_exact(shapes[k].n);   // (-1: a finish-only job)
         const bool is_long = lg > kLgLds;
         const size_t total = (size_t)shapes[k].T * (size_t)shapes[k].n;
-        const long long part_at = p_max[k] + p_max_any[k], part_end = p_max[k + 1] + p_max_any[k + 1];
         jobs[k] = FidJob{x_of[k], is_long ? buf.work + at_work : nullptr, buf.z + at_z, buf.u ? buf.u + at_u : nullptr,
-                         buf.v ? buf.v + at_u : nullptr, buf.rows ? buf.rows + k * kRow : nullptr, buf.part ? buf.part + part_at : nullptr,
+                         buf.v ? buf.v + at_u : nullptr, buf.rows ? buf.rows + k * kRow : nullptr, buf.part ? buf.part + p_max[k] : nullptr,
                          (int32_t)shapes[k].n_in, (int32_t)shapes[k].n, shapes[k].T, lg, lg < 0 ? 0 : lg / 2, lg < 0 ? 0 : lg - lg / 2,
-                         (int32_t)(part_end - part_at)};
+                         (int32_t)(p_max[k + 1] - p_max[k])};
         if (is_long) at_work += total;
         at_z += total;
         at_u += (size_t)shapes[k].n;
@@ -427,125 +426,29 @@ hipError_t fid_upload_tables(const FidDeviceTables &dst, hipStream_t st)
 hipError_t fid_launch_transforms(const FidPlan &plan, const FidJob *d_jobs, const long long *d_pref, const FidDeviceTables &tables,
                                  hipStream_t st)
 {
-    const size_t nk = plan.K;
-    const int K = (int)nk;
-    const long long *d_short = d_pref, *d_one = d_short + nk + 1, *d_two = d_one + nk + 1;
-    const dim3 block(kThreads);
+    const ItemTables &tab = plan.tab;
+    const int K = (int)tab.K;
     const size_t block_lds = 2 * (size_t)kLdsPoints * sizeof(double);
-    hipError_t e;
-    if (plan.items(kFidShort)) {
-        const int plane = std::max(plan.max_short, 16);   // (swz stays inside an aligned block of 16)
-        hipLaunchKernelGGL(fid_short_kernel, fid_item_grid(plan.items(kFidShort)), block, 2 * (size_t)plane * sizeof(double), st, d_jobs,
-                           d_short, K, plane, tables.tw);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    if (plan.items(kFidPass1)) {
-        hipLaunchKernelGGL(fid_pass1_kernel, fid_item_grid(plan.items(kFidPass1)), block, block_lds, st, d_jobs, d_one, K, tables.tw,
-                           tables.hi, tables.lo);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(fid_pass2_kernel, fid_item_grid(plan.items(kFidPass2)), block, block_lds, st, d_jobs, d_two, K, tables.tw);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    const int plane = std::max(plan.max_short, 16);   // (swz stays inside an aligned block of 16)
+    hipError_t e = launch_items(fid_short_kernel, tab.items(kFidShort), kThreads, 2 * (size_t)plane * sizeof(double), st, d_jobs,
+                                tab.device(d_pref, kFidShort), K, plane, tables.tw);
+    if (e != hipSuccess) return e;
+    e = launch_items(fid_pass1_kernel, tab.items(kFidPass1), kThreads, block_lds, st, d_jobs, tab.device(d_pref, kFidPass1), K,
+                     tables.tw, tables.hi, tables.lo);
+    if (e != hipSuccess) return e;
+    return launch_items(fid_pass2_kernel, tab.items(kFidPass2), kThreads, block_lds, st, d_jobs, tab.device(d_pref, kFidPass2), K,
+                        tables.tw);
 }
 
 hipError_t fid_launch_finish(const FidPlan &plan, const FidJob *d_jobs, const long long *d_pref, hipStream_t st)
 {
-    const size_t nk = plan.K;
-    const int K = (int)nk;
-    const long long *d_max = d_pref + (size_t)kFidMaxPart * (nk + 1), *d_fin = d_pref + (size_t)kFidFinish * (nk + 1);
-    const dim3 block(kThreads);
-    hipError_t e;
-    if (plan.items(kFidMaxPart)) {   // (finish-only jobs have theirs from fid_any.hip)
-        hipLaunchKernelGGL(fid_max_part_kernel, fid_item_grid(plan.items(kFidMaxPart)), block, 0, st, d_jobs, d_max, K);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), block, 0, st, d_jobs);
+    const ItemTables &tab = plan.tab;
+    const int K = (int)tab.K;
+    hipError_t e = launch_items(fid_max_part_kernel, tab.items(kFidMaxPart), kThreads, 0, st, d_jobs, tab.device(d_pref, kFidMaxPart), K);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fid_max_kernel, dim3((unsigned)K), dim3(kThreads), 0, st, d_jobs);   // (a workgroup per spectrum)
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(fid_finish_kernel, fid_item_grid(plan.items(kFidFinish)), block, 0, st, d_jobs, d_fin, K);
-    return hipGetLastError();
+    return launch_items(fid_finish_kernel, tab.items(kFidFinish), kThreads, 0, st, d_jobs, tab.device(d_pref, kFidFinish), K);
 }
 
 }  // namespace nmrfit
-
-using namespace nmrfit;
-
-#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
-
-int nmrfit_fid_transform(int device, int32_t K, const int64_t *n_in, const int64_t *n, const int32_t *T, const double *fid,
-                         double *u_out, double *v_out, double *rows_out, double *transform_out)
-{
-    const std::string who = "nmrfit_fid_transform";
-    if (K <= 0 || !n_in || !n || !T || !fid || !u_out || !v_out || !rows_out)
-        return refuse(NMRFIT_E_INVALID, who + ": the number of spectra must be > 0 and n_in, n, T, fid, u_out, v_out, rows_out non-null");
-    for (int32_t k = 0; k < K; ++k) {
-        if (T[k] <= 0 || n_in[k] <= 0)
-            return refuse(NMRFIT_E_INVALID, who + ": every spectrum needs T > 0 and n_in > 0 (spectrum " + std::to_string(k) + ")");
-        if (n[k] < n_in[k])
-            return refuse(NMRFIT_E_INVALID, who + ": a transform length is at least the trace's length (spectrum " + std::to_string(k) + ")");
-    }
-    const int64_t max_values = (int64_t)1 << 26;
-    int64_t values = 0;
-    for (int32_t k = 0; k < K; ++k) {
-        const int lg = fid_log2_exact(n[k]);
-        if (lg < 1 || lg > kLgMax)
-            return refuse(NMRFIT_E_UNSUPPORTED, who + ": a transform length is a power of two, 2 .. 2^" + std::to_string(kLgMax) +
-                                                    " (spectrum " + std::to_string(k) + "): zero fill to the next power of two");
-        if (values <= max_values) values += (int64_t)T[k] * n[k];   // (each term < 2^53: the sum cannot overflow)
-    }
-    if (K > kWeightsMaxSpectra || values > max_values)
-        return refuse(NMRFIT_E_UNSUPPORTED, who + ": a call takes at most " + std::to_string(kWeightsMaxSpectra) + " spectra and " +
-                                                std::to_string(max_values) + " transformed values (T n summed over the spectra)");
-    int rc = use_device(device);
-    if (rc != NMRFIT_OK) return rc;
-    StreamLease lease(device);
-    NMRFIT_HIP(lease.take());
-    hipStream_t st = lease.s;
-
-    const size_t nk = (size_t)K;
-    std::vector<FidShape> shapes(nk);
-    for (size_t k = 0; k < nk; ++k) shapes[k] = FidShape{n_in[k], n[k], T[k]};
-    const FidPlan plan = fid_plan(shapes.data(), nk);
-    Scratch mem;   // one allocation for the call's buffers
-    Carver c;
-    const size_t o_jobs = c.take(nk * sizeof(FidJob)), o_pref = c.take(plan.pref.size() * sizeof(long long));
-    const size_t o_tw = c.take(kFidStage * sizeof(FidTw)), o_hi = c.take(kFidSplit * sizeof(FidTwDD)),
-                 o_lo = c.take(kFidSplit * sizeof(FidTwDD));
-    const size_t o_x = c.take((size_t)plan.in_values * sizeof(double2)), o_work = c.take((size_t)plan.work_values * sizeof(double2));
-    const size_t o_z = c.take((size_t)plan.values * sizeof(double2)), o_u = c.take((size_t)plan.points * sizeof(double)),
-                 o_v = c.take((size_t)plan.points * sizeof(double));
-    const size_t o_rows = c.take(nk * kRow * sizeof(double)), o_part = c.take((size_t)plan.items(kFidMaxPart) * sizeof(double4));
-    unsigned char *base = nullptr;
-    NMRFIT_HIP(mem.alloc(&base, c.total));
-    FidJob *d_jobs = reinterpret_cast<FidJob *>(base + o_jobs);
-    long long *d_pref = reinterpret_cast<long long *>(base + o_pref);
-    const FidDeviceTables tables{reinterpret_cast<FidTw *>(base + o_tw), reinterpret_cast<FidTwDD *>(base + o_hi),
-                                 reinterpret_cast<FidTwDD *>(base + o_lo)};
-    double2 *d_x = reinterpret_cast<double2 *>(base + o_x);
-    const FidBuffers buf{reinterpret_cast<double2 *>(base + o_work), reinterpret_cast<double2 *>(base + o_z),
-                         reinterpret_cast<double *>(base + o_u),     reinterpret_cast<double *>(base + o_v),
-                         reinterpret_cast<double *>(base + o_rows),  reinterpret_cast<double4 *>(base + o_part)};
-    std::vector<const double2 *> x_of(nk);
-    {
-        size_t at_x = 0;
-        for (size_t k = 0; k < nk; ++k) {
-            x_of[k] = d_x + at_x;
-            at_x += (size_t)T[k] * (size_t)n_in[k];
-        }
-    }
-    const std::vector<FidJob> jobs = fid_job_table(plan, shapes.data(), x_of.data(), buf);
-    // (pageable host memory: the copies have left the host arrays when hipMemcpyAsync returns)
-    NMRFIT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), nk * sizeof(FidJob), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_pref, plan.pref.data(), plan.pref.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(fid_upload_tables(tables, st));
-    NMRFIT_HIP(hipMemcpyAsync(d_x, fid, (size_t)plan.in_values * sizeof(double2), hipMemcpyHostToDevice, st));
-    NMRFIT_HIP(fid_launch_transforms(plan, d_jobs, d_pref, tables, st));
-    NMRFIT_HIP(fid_launch_finish(plan, d_jobs, d_pref, st));
-    if ((rc = staged_d2h(device, st, rows_out, buf.rows, nk * kRow * sizeof(double))) != NMRFIT_OK) return rc;
-    if ((rc = staged_d2h(device, st, u_out, buf.u, (size_t)plan.points * sizeof(double))) != NMRFIT_OK) return rc;
-    if ((rc = staged_d2h(device, st, v_out, buf.v, (size_t)plan.points * sizeof(double))) != NMRFIT_OK) return rc;
-    if (transform_out) return staged_d2h(device, st, transform_out, buf.z, (size_t)plan.values * sizeof(double2));
-    return NMRFIT_OK;
-}
-
-#pragma GCC visibility pop

@@ -6,25 +6,21 @@
 //   fida_filter_kernel     (b) b[k] = conj(c[k]), b[M - k] = conj(c[k]), 0 elsewhere: once per distinct N of the call
 //   fida_product_kernel    (c) P[q] = A[q] B[q] in natural order; both operands are read through the permutation the
 //                          transform kernels store with: entry M - 1 - (q ^ M/2) holds the value of index q
-//   fida_max_part_kernel   the partial maxima of the finishing stage for rows of N points (fid.hip's take n for a power of
-//                          two): one wave per 8192 values, the reduction by shuffles
 //   fida_store_kernel      (d) X[q] = fft(P)[(-q) mod M] / M * c[q] read through the same permutation, stored centred
 //                          and reversed: Z[j] = Y[N - 1 - j], Y[i] = X[(i + N - floor(N/2)) mod N]
 // Every launch is a flat list of work items (1024 points of a trace) found by the prefix-table search of fid.hip; a
 // launch without items is not made.  The permuted reads flip the top bit of the index and reverse the order: 64
 // consecutive lanes read 64 consecutive values on every side.  No LDS, no atomics, no scratch memory.  The chirp values
-// are the host's table (fid_chirp.h), one per distinct N.
+// are the host's table (fid_chirp.h), one per distinct N.  The spectra of the stage are FINISH-ONLY jobs of the call's
+// main job table: fid.hip's finishing launches take their Z from (d).
 // P overwrites a (dead once A is stored) and fft(P) overwrites A (dead once P is stored): two planes of T M values per
 // spectrum.  The filter's transform B is a job (T = 1) of the same launches as the A transforms.
-#include "fid_any_internal.h"
 #include "fid_chirp.h"
 #include "fid_device.h"
+#include "fid_internal.h"
 #include "nmrfit_amd_fid_any.h"
 
-#include <climits>
-#include <cmath>
 #include <map>
-#include <string>
 #include <vector>
 
 namespace nmrfit {
@@ -33,8 +29,6 @@ namespace {
 #pragma clang fp contract(off)   // (every product and sum of the definition is rounded once)
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 1024;   // points of a trace per work item
-constexpr int kMaxChunk = 8192;   // values per partial maximum (fid.hip's)
 
 // What the stages read and write: one record per spectrum on the chirp path, then one per distinct N (the filter's).
 // Every pointer is device memory.
@@ -51,28 +45,19 @@ struct AnyJob {
 
 enum { kLoad = 0, kFilter = 1, kProduct = 2, kStore = 3, kAnyTables = 4 };
 
-// the item's trace and first point: a trace of `len` points is ceil(len / 1024) items
-__device__ __forceinline__ void item_place(long long local, int len, long long *t, int *from)
-{
-    const int chunks = (len + kChunk - 1) / kChunk;
-    *t = local / chunks;
-    *from = (int)(local - *t * chunks) * kChunk;
-}
-
 __global__ __launch_bounds__(kThreads) void fida_load_kernel(const AnyJob *__restrict__ jobs, const long long *__restrict__ pref, int K)
 {
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const AnyJob &q = jobs[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const AnyJob &q = jobs[at.k];
     const int M = q.M, n_in = q.n_in;
     long long t;
     int from;
-    item_place(item - pref[k], M, &t, &from);
+    item_place(at.local(), M, &t, &from);
     const double2 *__restrict__ x = q.x + t * n_in;
     const FidTw *__restrict__ c = q.c;
     double2 *__restrict__ a = q.a + t * M;
-    for (int i = from + (int)threadIdx.x; i < M && i < from + kChunk; i += kThreads) {
+    for (int i = from + (int)threadIdx.x; i < M && i < from + kFidChunk; i += kThreads) {
         double2 out = make_double2(0.0, 0.0);
         if (i < n_in) {
             const double2 val = x[i];
@@ -86,15 +71,14 @@ __global__ __launch_bounds__(kThreads) void fida_load_kernel(const AnyJob *__res
 
 __global__ __launch_bounds__(kThreads) void fida_filter_kernel(const AnyJob *__restrict__ jobs, const long long *__restrict__ pref, int K)
 {
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const AnyJob &q = jobs[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const AnyJob &q = jobs[at.k];
     const int M = q.M, N = q.N;
-    const int from = (int)(item - pref[k]) * kChunk;
+    const int from = (int)at.local() * kFidChunk;
     const FidTw *__restrict__ c = q.c;
     double2 *__restrict__ b = q.a;
-    for (int i = from + (int)threadIdx.x; i < M && i < from + kChunk; i += kThreads) {
+    for (int i = from + (int)threadIdx.x; i < M && i < from + kFidChunk; i += kThreads) {
         double2 out = make_double2(0.0, 0.0);
         const int at = i < N ? i : (M - i < N ? M - i : -1);   // (M >= 2 N - 1: the two runs do not meet)
         if (at >= 0) {
@@ -108,18 +92,17 @@ __global__ __launch_bounds__(kThreads) void fida_filter_kernel(const AnyJob *__r
 __global__ __launch_bounds__(kThreads) void fida_product_kernel(const AnyJob *__restrict__ jobs, const long long *__restrict__ pref,
                                                                 int K)
 {
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const AnyJob &q = jobs[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const AnyJob &q = jobs[at.k];
     const int M = q.M, half = M >> 1;
     long long t;
     int from;
-    item_place(item - pref[k], M, &t, &from);
+    item_place(at.local(), M, &t, &from);
     const double2 *__restrict__ A = q.A + t * M;
     const double2 *__restrict__ B = q.B;
     double2 *__restrict__ P = q.a + t * M;
-    for (int i = from + (int)threadIdx.x; i < M && i < from + kChunk; i += kThreads) {
+    for (int i = from + (int)threadIdx.x; i < M && i < from + kFidChunk; i += kThreads) {
         const int e = M - 1 - (i ^ half);
         const double2 va = A[e], vb = B[e];
         const Cx out = cmul(Cx{va.x, va.y}, Cx{vb.x, vb.y});
@@ -129,19 +112,18 @@ __global__ __launch_bounds__(kThreads) void fida_product_kernel(const AnyJob *__
 
 __global__ __launch_bounds__(kThreads) void fida_store_kernel(const AnyJob *__restrict__ jobs, const long long *__restrict__ pref, int K)
 {
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const AnyJob &q = jobs[k];
+    ItemAt at;
+    if (!item_at(pref, K, &at)) return;
+    const AnyJob &q = jobs[at.k];
     const int M = q.M, half = M >> 1, N = q.N, turn = N - (N >> 1);
     const double inv_m = q.inv_m;
     long long t;
     int from;
-    item_place(item - pref[k], N, &t, &from);
+    item_place(at.local(), N, &t, &from);
     const double2 *__restrict__ p = q.A + t * M;
     const FidTw *__restrict__ c = q.c;
     double2 *__restrict__ z = q.z + t * N;
-    for (int j = from + (int)threadIdx.x; j < N && j < from + kChunk; j += kThreads) {
+    for (int j = from + (int)threadIdx.x; j < N && j < from + kFidChunk; j += kThreads) {
         // Z[j] = Y[i], i = N - 1 - j;  Y[i] = X[(i + N - floor(N/2)) mod N]
         int xq = N - 1 - j + turn;
         if (xq >= N) xq -= N;
@@ -152,47 +134,6 @@ __global__ __launch_bounds__(kThreads) void fida_store_kernel(const AnyJob *__re
         z[j] = make_double2(out.re, out.im);
     }
 }
-
-// The lexicographic maximum and a not-finite flag of 8192 values of a spectrum whose n is any length: fid.hip's partial
-// maximum with the point within the trace as a remainder, not a mask (one 64-bit division per item, a 32-bit one per
-// value).  One wave per item: the reduction is the wave's shuffles alone (maxima are exact: the order is free).
-__global__ __launch_bounds__(kWave) void fida_max_part_kernel(const FidJob *__restrict__ jobs, const long long *__restrict__ pref, int K)
-{
-    const long long item = work_item(pref[K]);
-    if (item < 0) return;
-    const int k = find_job(pref, K, item);
-    const FidJob &q = jobs[k];
-    const int chunk = (int)(item - pref[k]);
-    const unsigned n = (unsigned)q.n;
-    const long long total = (long long)q.T * n, from = (long long)chunk * kMaxChunk;
-    const int count = (int)(from + kMaxChunk < total ? kMaxChunk : total - from);
-    const long long t0 = from / n;
-    const unsigned j0 = (unsigned)(from - t0 * n);
-    const double2 *__restrict__ z = q.z + from;
-    double best_re = -INFINITY, best_im = -INFINITY;
-    long long best_idx = LLONG_MAX;
-    int bad = 0;
-    const auto take = [&](double re, double im, long long idx, int b) {
-        const bool better = re > best_re || (re == best_re && (im > best_im || (im == best_im && idx < best_idx)));
-        if (better) {
-            best_re = re;
-            best_im = im;
-            best_idx = idx;
-        }
-        bad |= b;
-    };
-    for (int i = threadIdx.x; i < count; i += kWave) {
-        const double2 val = z[i];
-        const unsigned at = j0 + (unsigned)i, dt = at / n, j = at - dt * n;   // (at < n + 8192 < 2^32)
-        // (Z[t n + j] is Y[t n + n - 1 - j])
-        take(val.x, val.y, (t0 + dt) * (long long)n + (n - 1 - j), !(isfinite(val.x) && isfinite(val.y)));
-    }
-    for (int o = kWave / 2; o > 0; o >>= 1)
-        take(__shfl_xor(best_re, o), __shfl_xor(best_im, o), __shfl_xor(best_idx, o), __shfl_xor(bad, o));
-    if (threadIdx.x == 0) q.part[chunk] = make_double4(best_re, best_im, bad ? 0.0 : (double)best_idx, bad ? 1.0 : 0.0);
-}
-
-long long trace_items(int64_t T, int64_t len) { return T * ((len + kChunk - 1) / kChunk); }
 
 }  // namespace
 
@@ -218,7 +159,7 @@ struct FidAnyStage::Impl {
     std::vector<FidTw> chirp;           // the chirp tables, one after the other
     std::vector<FidShape> shapes_ab;    // the first transforms: every spectrum's a (T planes), then every filter (T = 1)
     FidPlan plan_ab, plan_p;            // ... and the transform of P: the spectra alone
-    std::vector<long long> pref;        // kAnyTables prefix tables over the records
+    ItemTables tab;                     // kAnyTables prefix tables over the records
     size_t o_jobs_ab = 0, o_jobs_p = 0, o_pref_ab = 0, o_pref_p = 0, o_recs = 0, o_pref = 0, o_chirp = 0, o_a = 0, o_z = 0, o_work = 0;
     // device memory, set by upload()
     const FidJob *d_jobs_ab = nullptr, *d_jobs_p = nullptr;
@@ -258,16 +199,15 @@ void FidAnyStage::plan(const std::vector<FidAnyAsk> &asks)
     }
     s.plan_ab = fid_plan(s.shapes_ab.data(), nr);
     s.plan_p = fid_plan(s.shapes_ab.data(), na);
-    s.pref.assign((size_t)kAnyTables * (nr + 1), 0);
-    long long *p_load = s.pref.data(), *p_filter = p_load + nr + 1, *p_product = p_filter + nr + 1, *p_store = p_product + nr + 1;
+    s.tab = ItemTables(kAnyTables, nr);
     for (size_t r = 0; r < nr; ++r) {
         const bool spectrum = r < na;
         const int64_t M = s.shapes_ab[r].n;
         const int64_t T = s.shapes_ab[r].T;
-        p_load[r + 1] = p_load[r] + (spectrum ? trace_items(T, M) : 0);
-        p_filter[r + 1] = p_filter[r] + (spectrum ? 0 : trace_items(1, M));
-        p_product[r + 1] = p_product[r] + (spectrum ? trace_items(T, M) : 0);
-        p_store[r + 1] = p_store[r] + (spectrum ? trace_items(T, asks[r].N) : 0);
+        s.tab.add(kLoad, r, spectrum ? trace_items(T, M) : 0);
+        s.tab.add(kFilter, r, spectrum ? 0 : trace_items(1, M));
+        s.tab.add(kProduct, r, spectrum ? trace_items(T, M) : 0);
+        s.tab.add(kStore, r, spectrum ? trace_items(T, asks[r].N) : 0);
     }
 }
 
@@ -278,10 +218,10 @@ void FidAnyStage::carve(Carver &c)
     const size_t na = s.asks.size(), nr = s.records();
     s.o_jobs_ab = c.take(nr * sizeof(FidJob));
     s.o_jobs_p = c.take(na * sizeof(FidJob));
-    s.o_pref_ab = c.take(s.plan_ab.pref.size() * sizeof(long long));
-    s.o_pref_p = c.take(s.plan_p.pref.size() * sizeof(long long));
+    s.o_pref_ab = c.take(s.plan_ab.tab.bytes());
+    s.o_pref_p = c.take(s.plan_p.tab.bytes());
     s.o_recs = c.take(nr * sizeof(AnyJob));
-    s.o_pref = c.take(s.pref.size() * sizeof(long long));
+    s.o_pref = c.take(s.tab.bytes());
     s.o_chirp = c.take(s.chirp.size() * sizeof(FidTw));
     s.o_a = c.take((size_t)s.plan_ab.values * sizeof(double2));      // a / P of every spectrum, then b of every distinct N
     s.o_z = c.take((size_t)s.plan_ab.values * sizeof(double2));      // A / fft(P) of every spectrum, then B
@@ -335,10 +275,10 @@ hipError_t FidAnyStage::upload(unsigned char *base, const double2 *const *x_of, 
     hipError_t e;
     if ((e = hipMemcpyAsync(d_jobs_ab, jobs_ab.data(), nr * sizeof(FidJob), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(d_jobs_p, jobs_p.data(), na * sizeof(FidJob), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_pref_ab, s.plan_ab.pref.data(), s.plan_ab.pref.size() * sizeof(long long), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_pref_p, s.plan_p.pref.data(), s.plan_p.pref.size() * sizeof(long long), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(d_pref_ab, s.plan_ab.tab.pref.data(), s.plan_ab.tab.bytes(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(d_pref_p, s.plan_p.tab.pref.data(), s.plan_p.tab.bytes(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(d_recs, recs.data(), nr * sizeof(AnyJob), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_pref, s.pref.data(), s.pref.size() * sizeof(long long), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(d_pref, s.tab.pref.data(), s.tab.bytes(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(const_cast<FidTw *>(d_chirp), s.chirp.data(), s.chirp.size() * sizeof(FidTw), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     s.d_jobs_ab = d_jobs_ab;
     s.d_jobs_p = d_jobs_p;
@@ -349,47 +289,22 @@ hipError_t FidAnyStage::upload(unsigned char *base, const double2 *const *x_of, 
     return hipSuccess;
 }
 
-hipError_t FidAnyStage::launch(const FidDeviceTables &tables, const FidPlan &main_plan, const FidJob *d_main_jobs,
-                               const long long *d_main_pref, hipStream_t st) const
+hipError_t FidAnyStage::launch(const FidDeviceTables &tables, hipStream_t st) const
 {
     const Impl &s = *impl_;
     if (s.asks.empty()) return hipSuccess;
-    const size_t nr = s.records();
-    const int R = (int)nr;
-    const long long *p_load = s.pref.data(), *p_filter = p_load + nr + 1, *p_product = p_filter + nr + 1, *p_store = p_product + nr + 1;
-    const long long *d_load = s.d_pref, *d_filter = d_load + nr + 1, *d_product = d_filter + nr + 1, *d_store = d_product + nr + 1;
-    const dim3 block(kThreads);
+    const int R = (int)s.records();
+    const auto stage = [&](void (*kernel)(const AnyJob *, const long long *, int), int which) {
+        return launch_items(kernel, s.tab.items(which), kThreads, 0, st, s.d_recs, s.tab.device(s.d_pref, which), R);
+    };
     hipError_t e;
-    // ---- eleven launches: (a), (b), the transforms of a and b (3), (c), the transform of P (3), (d), the partial maxima
-    hipLaunchKernelGGL(fida_load_kernel, fid_item_grid(p_load[nr]), block, 0, st, s.d_recs, d_load, R);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(fida_filter_kernel, fid_item_grid(p_filter[nr]), block, 0, st, s.d_recs, d_filter, R);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    // ---- ten launches: (a), (b), the transforms of a and b (3), (c), the transform of P (3), (d)
+    if ((e = stage(fida_load_kernel, kLoad)) != hipSuccess) return e;
+    if ((e = stage(fida_filter_kernel, kFilter)) != hipSuccess) return e;
     if ((e = fid_launch_transforms(s.plan_ab, s.d_jobs_ab, s.d_pref_ab, tables, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(fida_product_kernel, fid_item_grid(p_product[nr]), block, 0, st, s.d_recs, d_product, R);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = stage(fida_product_kernel, kProduct)) != hipSuccess) return e;
     if ((e = fid_launch_transforms(s.plan_p, s.d_jobs_p, s.d_pref_p, tables, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(fida_store_kernel, fid_item_grid(p_store[nr]), block, 0, st, s.d_recs, d_store, R);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const size_t nk = main_plan.K;
-    hipLaunchKernelGGL(fida_max_part_kernel, fid_item_grid(main_plan.items(kFidMaxPartAny)), dim3(kWave), 0, st, d_main_jobs,
-                       d_main_pref + (size_t)kFidMaxPartAny * (nk + 1), (int)nk);
-    return hipGetLastError();
+    return stage(fida_store_kernel, kStore);
 }
 
 }  // namespace nmrfit
-
-using namespace nmrfit;
-
-#pragma GCC visibility push(default)   // the C-ABI: the only symbols the library exports (build.sh: -fvisibility=hidden)
-
-int nmrfit_fid_transform_any(int device, int32_t K, const int64_t *n_in, const int64_t *n, const int32_t *T, const double *fid,
-                             const int32_t *form, const double *g, const int32_t *window_of, int32_t M, const int64_t *window_len,
-                             const double *windows, double *u_out, double *v_out, double *rows_out, double *transform_out,
-                             double *conditioned_out)
-{
-    return fid_condition_transform_run("nmrfit_fid_transform_any", true, device, K, n_in, n, T, fid, form, g, window_of, M, window_len,
-                                       windows, u_out, v_out, rows_out, transform_out, conditioned_out);
-}
-
-#pragma GCC visibility pop

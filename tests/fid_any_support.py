@@ -67,6 +67,22 @@ def raw_call(L, n_in, n, T, x, form, g, window_of, windows, device=0, entry="nmr
     return rc, u, v, rows, Z, C
 
 
+# ---- ties across the chunks of the partial maxima --------------------------------------------------------------------
+
+# (name, n, T, placements of the larger trace).  A partial maximum is over 8192 values of a spectrum's Z: 700 traces of 12
+# points (a finish-only job: the point within the trace is a remainder) are 8400 values, and flat value 8192 is point 8 of
+# trace 682, which straddles the chunks; 1100 traces of 8 points (the mask) are 8800 values with the boundary at trace 1024.
+TIES = (("A", 12, 700, ((5, 682, 699), (682, 699), (699,))),
+        ("B", 8, 1100, ((5, 1024, 1099), (1024, 1099), (1099,))))
+
+
+def tie_stack(lo, T, hi_at):
+    """T copies of the row ``lo`` with 3 * lo at the traces ``hi_at``: equal traces tie in every value."""
+    x = np.repeat(np.asarray(lo).reshape(1, -1), T, axis=0)
+    x[list(hi_at)] = 3.0 * x[0]
+    return x
+
+
 # ---- the mixed batch -----------------------------------------------------------------------------------------------------
 
 def mixed_jobs():

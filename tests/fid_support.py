@@ -92,6 +92,18 @@ def same_result(got, want):
                                          for g, w in zip(got, want))
 
 
+def refusal_table(groups):
+    """The recorded refusals of an entry point, (code, the complete nmrfit_last_error() text, the calls that get it), as
+    {call: (code, text)}: the text of the library before the three entry points shared one body, which no later change
+    of the host code may alter."""
+    table = {}
+    for code, text, keys in groups:
+        for key in keys:
+            assert key not in table, key
+            table[key] = (code, text)
+    return table
+
+
 # ---- the LDS swizzle of csrc/fid.hip, restated ---------------------------------------------------------------------------
 
 def swz(a):

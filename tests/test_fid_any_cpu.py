@@ -3,7 +3,7 @@ CPU tier of the any-length FID transform (nmrfit_amd/fid.py, csrc/fid_any.hip, c
 include/nmrfit_amd_fid_any.h): the numpy restatement of the chirp-z definition against numpy's own transform of the same
 length within the header's bar, the centring by index for odd and even N, the chirp values' stated bound against a truth
 of 113 bits, the lengths transform_length takes, the ctypes table against the header, the library's refusals (made
-before any device work) and the new kernels' resources.
+before any device work) and the kernels' resources.
 
 Measured here: the chirp values of csrc/fid_chirp.h are within 0.7067 u of the exact ones (mu = 1 u) over the eight
 lengths; a table filled from pi k^2 / N formed in fp64 is off by 1.3e7 u at N = 2^21 - 1.
@@ -95,6 +95,19 @@ def test_centring_is_fftshift_by_index_for_odd_and_even_lengths(N):
         assert np.abs(Y - np.exp(-2j * np.pi * ((d * q) % N) / N)).max() <= 1e-9
 
 
+def test_the_mirror_gives_a_tie_to_the_first_copy():
+    """The host side of tests/test_gpu_fid_any.py's tie construction (fa.TIES): of equal rows of a stacked Y, finish_host
+    takes the maximum in the first, wherever the copies lie."""
+    for name, n, T, placements in fa.TIES:
+        row = fid.bluestein_host(fs.sample_fid(n, 1, seed=97), n)[0]
+        assert (8192 // n) in placements[0] and T * n > 8192 and row.real.max() > 0.0
+        for hi_at in placements:
+            Y = fa.tie_stack(row, T, hi_at)
+            u, v, out = fid.finish_host(Y)
+            assert out[0] == 0 and int(out[3]) // n == hi_at[0] and int(out[3]) % n == int(np.argmax(row.real)), (name, hi_at)
+            assert complex(out[1], out[2]) == Y[hi_at[0], int(out[3]) % n] == np.max(Y)
+
+
 def test_transform_length_takes_any_length_on_request_only():
     for n in HOST_LENGTHS + (65466, (1 << 21) - 1):
         assert fid.transform_length(n, None, any_length=True) == n
@@ -157,9 +170,44 @@ def test_the_entry_points_are_chosen_by_the_lengths_of_a_call(monkeypatch):
     assert calls == [("plain", 10), ("cond", 17), ("any", 17), ("any", 17), ("any", 17)]
 
 
+# recorded from the library before the three entry points shared one body (tests/fid_support.refusal_table)
+REFUSALS = fs.refusal_table([
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_transform_any: form 2 (spectrum) needs a transform length that is a power of two '
+     '(spectrum 1): its ramp tables are split at 2^11; use form 1 (fid), or zero fill',
+     ('form 2 at n = 12',)),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_transform_any: a transform length is a power of two, 2 .. 2^22, or any other length, 3 ..'
+     ' 2^21 - 1 (spectrum 1)',
+     ('n = 2^21 + 1', 'n = 1', 'n = 2^23')),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_transform_any: a transform length is at least the conditioned trace's length (spectrum 0)",
+     ("n < n_in'",)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_transform_any: every spectrum needs T > 0 and n_in > 0 (spectrum 1)',
+     ('T = 0',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_transform_any: form is 0 (none), 1 (fid) or 2 (spectrum) (spectrum 1)',
+     ('form = 3', 'form = 3 and n = 2^21 + 1')),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_transform_any: a call takes at most 65535 spectra and 67108864 transformed values (T n '
+     'summed over the spectra, plus T n_in of those in form 1, plus 2 T M of those whose n is no power of '
+     'two and 2 M per distinct such n)',
+     ('6 traces of 2^21 - 1', '2^26 values and a chirp job')),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_condition_transform: a transform length is a power of two, 2 .. 2^22 (spectrum 0): zero '
+     'fill to the next power of two',
+     ('n = 12 at the old entry point',)),
+])
+
+
+def _refusal_is_the_recorded_one(key, rc, message):
+    assert (rc, message.decode()) == REFUSALS[key], key
+
+
 def test_argument_validation_needs_no_gpu():
-    """Every refusal of the new entry point comes back before anything touches a device, with its code and a message
-    naming the spectrum; a valid call reports the missing device (or, with a GPU, nothing)."""
+    """Every refusal of the new entry point comes back before anything touches a device, with the code and the complete
+    message of REFUSALS; a valid call reports the missing device (or, with a GPU, nothing)."""
     L = _cabi.lib()
     base = dict(n_in=[64, 10, 5], n=[57, 12, 8], T=[2, 1, 1], x=np.zeros(2 * (2 * 64 + 10 + 5)), form=[1, 0, 2], g=[5.0, 0.0, 3.3],
                 window_of=[0, -1, -1], windows=[np.linspace(1.0, 0.5, 57)])
@@ -170,34 +218,32 @@ def test_argument_validation_needs_no_gpu():
         return fa.raw_call(L, a["n_in"], a["n"], a["T"], a["x"], a["form"], a["g"], a["window_of"], a["windows"],
                            device=a.get("device", 0))[0]
 
-    def refused(code, word, **kw):
-        assert call(**kw) == code, kw
-        msg = L.nmrfit_last_error()
-        assert word in msg and b"nmrfit_fid_transform_any" in msg, (kw, msg)
+    def refused(key, **kw):
+        _refusal_is_the_recorded_one(key, call(**kw), L.nmrfit_last_error())
     assert call() in (_cabi.OK, _cabi.E_NO_DEVICE)
     assert call(device=1 << 20) == _cabi.E_NO_DEVICE
     # form 2 at a length that is no power of two
-    refused(_cabi.E_UNSUPPORTED, b"form 2", form=[1, 2, 2], g=[5.0, 1.5, 3.3])
-    assert b"spectrum 1" in L.nmrfit_last_error() and b"power of two" in L.nmrfit_last_error()
+    refused("form 2 at n = 12", form=[1, 2, 2], g=[5.0, 1.5, 3.3])
     # the lengths
-    refused(_cabi.E_UNSUPPORTED, b"2^21 - 1", n=[57, (1 << 21) + 1, 8])
-    assert b"spectrum 1" in L.nmrfit_last_error()
-    refused(_cabi.E_UNSUPPORTED, b"2^21 - 1", n_in=[64, 1, 5], n=[57, 1, 8], x=np.zeros(2 * (2 * 64 + 1 + 5)))
-    refused(_cabi.E_UNSUPPORTED, b"2^21 - 1", n=[57, 1 << 23, 8])
+    refused("n = 2^21 + 1", n=[57, (1 << 21) + 1, 8])
+    refused("n = 1", n_in=[64, 1, 5], n=[57, 1, 8], x=np.zeros(2 * (2 * 64 + 1 + 5)))
+    refused("n = 2^23", n=[57, 1 << 23, 8])
     assert call(n=[57, (1 << 21) - 1, 8]) in (_cabi.OK, _cabi.E_NO_DEVICE)
     # those of nmrfit_fid_condition_transform still hold
-    refused(_cabi.E_INVALID, b"at least", n=[56, 12, 8])                              # n < n_in' = 57
-    refused(_cabi.E_INVALID, b"spectrum 1", T=[2, 0, 1])
-    refused(_cabi.E_INVALID, b"form is 0", form=[1, 3, 2])
+    refused("n < n_in'", n=[56, 12, 8])                                               # n < n_in' = 57
+    refused("T = 0", T=[2, 0, 1])
+    refused("form = 3", form=[1, 3, 2])
     # the budget: T n + 2 T M + 2 M, M = 2^22 at n = 2^21 - 1
     one = dict(n_in=[1], x=np.zeros(2), form=[0], g=[0.0], window_of=[-1], windows=[])
-    refused(_cabi.E_UNSUPPORTED, b"2 T M", n=[(1 << 21) - 1], T=[6], **one)            # 6 (n + 2 M) + 2 M > 2^26 = 16 M
+    refused("6 traces of 2^21 - 1", n=[(1 << 21) - 1], T=[6], **one)                   # 6 (n + 2 M) + 2 M > 2^26 = 16 M
     # (5 (n + 2 M) + 2 M < 2^26 is taken: tests/test_gpu_fid_any.py's probe sizes are run once, outside the suite)
-    refused(_cabi.E_UNSUPPORTED, b"2 T M", n_in=[1, 1], n=[4099, 1 << 22], T=[1, 16], x=np.zeros(4), form=[0, 0], g=[0.0, 0.0],
+    refused("2^26 values and a chirp job", n_in=[1, 1], n=[4099, 1 << 22], T=[1, 16], x=np.zeros(4), form=[0, 0], g=[0.0, 0.0],
             window_of=[-1, -1], windows=[])                                            # 2^26 of the second alone: the first's on top
+    # a call that is wrong in two ways: the first refusal of the header's order wins
+    refused("form = 3 and n = 2^21 + 1", form=[1, 3, 2], n=[57, (1 << 21) + 1, 8])
     # the old entry point refuses what it refused, in its own words
     rc = fa.raw_call(L, [10], [12], [1], np.zeros(20), [0], [0.0], [-1], [], entry="nmrfit_fid_condition_transform")[0]
-    assert rc == _cabi.E_UNSUPPORTED and b"zero fill to the next power of two" in L.nmrfit_last_error()
+    _refusal_is_the_recorded_one("n = 12 at the old entry point", rc, L.nmrfit_last_error())
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
@@ -232,14 +278,13 @@ def test_the_chirp_values_are_within_the_stated_bound(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_kernel_resources():
-    """tools/kernel_resources.py --check --unit fid_any.hip: five kernels with the prefix fida_, none with scratch memory,
-    spills or LDS."""
+    """tools/kernel_resources.py --check --unit fid_any.hip: four kernels with the prefix fida_ (the partial maxima of its
+    spectra are fid.hip's fid_max_part_kernel's), none with scratch memory, spills or LDS."""
     run = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "--check", "--unit", "fid_any.hip"],
                          capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
     lines = [ln.split() for ln in run.stdout.splitlines()[1:] if ln.strip()]
-    assert sorted(ln[0] for ln in lines) == ["fida_filter_kernel", "fida_load_kernel", "fida_max_part_kernel", "fida_product_kernel",
-                                             "fida_store_kernel"], run.stdout
+    assert sorted(ln[0] for ln in lines) == ["fida_filter_kernel", "fida_load_kernel", "fida_product_kernel", "fida_store_kernel"], run.stdout
     for ln in lines:      # kernel VGPR AGPR scratch waves LDS s-spill
         assert int(ln[3]) == 0 and int(ln[6]) == 0 and int(ln[5]) == 0, ln
     print(run.stdout)

@@ -52,9 +52,87 @@ def test_table_and_header():
     assert fid.condition_host is nmrfit_amd.fid.condition_host
 
 
+# recorded from the library before the three entry points shared one body (tests/fid_support.refusal_table)
+REFUSALS = fs.refusal_table([
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: every spectrum needs T > 0 and n_in > 0 (spectrum 1)',
+     ('T = 0',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: every spectrum needs T > 0 and n_in > 0 (spectrum 2)',
+     ('n_in = -5',)),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_condition_transform: a transform length is at least the conditioned trace's length "
+     '(spectrum 1)',
+     ("n < n_in', spectrum 1",)),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_condition_transform: a transform length is at least the conditioned trace's length "
+     '(spectrum 2)',
+     ("n < n_in', spectrum 2",)),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_condition_transform: a transform length is a power of two, 2 .. 2^22 (spectrum 2): zero '
+     'fill to the next power of two',
+     ('n = 12', 'n = 2^23')),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_condition_transform: a transform length is at least the conditioned trace's length "
+     '(spectrum 0)',
+     ("n < n_in', spectrum 0",)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: form is 0 (none), 1 (fid) or 2 (spectrum) (spectrum 1)',
+     ('form = 3', 'form = 3 and n = 12')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: form is 0 (none), 1 (fid) or 2 (spectrum) (spectrum 0)',
+     ('form = -1',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: a group delay is finite and > 0 where a form is set (spectrum 1)',
+     ('g = 0.0, spectrum 1', 'g = -1.0, spectrum 1', 'g = nan, spectrum 1', 'g = inf, spectrum 1')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: a group delay is finite and > 0 where a form is set (spectrum 0)',
+     ('g = 0.0, spectrum 0', 'g = -1.0, spectrum 0', 'g = nan, spectrum 0', 'g = inf, spectrum 0')),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_condition_transform: form 1 (fid) needs a trace length that is a power of two, 2 .. 2^22 '
+     '(spectrum 0): use form 2 (spectrum)',
+     ('form 1 at 48 points',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: form 1 (fid) needs a trace of at least 2 floor(g + 2) points '
+     '(spectrum 0)',
+     ('g = 31 at 64 points', 'g = 1e300')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: window_of is -1 or the index of a window (spectrum 1)',
+     ('window_of = 2',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: window_of is -1 or the index of a window (spectrum 0)',
+     ('window_of = -2',)),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: a window has as many values as the conditioned trace has points '
+     '(spectrum 0)',
+     ('10 values for 57 points', '64 values for 57 points')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: a window value is not finite (window 1)',
+     ('a window value is nan', 'a window value is inf', 'a window value is -inf',
+      'a window value is nan and n = 12')),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_condition_transform: a call takes at most 65535 spectra and 67108864 transformed values '
+     '(T n summed over the spectra, plus T n_in of those in form 1)',
+     ('17 x 2^22 values', '9 x 2^22 values in form 1')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: the number of spectra must be > 0 and n_in, n, T, fid, form, g, '
+     'window_of, u_out, v_out, rows_out non-null',
+     ('argument 0 null', 'argument 1 null', 'argument 2 null', 'argument 3 null', 'argument 4 null',
+      'argument 5 null', 'argument 6 null', 'argument 10 null', 'argument 11 null', 'argument 12 null', 'K = 0')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_condition_transform: the number of windows must be >= 0, and window_len and windows '
+     'non-null when it is > 0',
+     ('M = 1 without arrays', 'M = -1')),
+])
+
+
+def _refusal_is_the_recorded_one(key, rc, message):
+    assert (rc, message.decode()) == REFUSALS[key], key
+
+
 def test_argument_validation_needs_no_gpu():
-    """Every refusal of the header comes back before anything touches a device, with its code and a message naming the
-    spectrum; a valid call reports the missing device (or, with a GPU, nothing)."""
+    """Every refusal of the header comes back before anything touches a device, with the code and the complete message of
+    REFUSALS; a valid call reports the missing device (or, with a GPU, nothing)."""
     L = _cabi.lib()
     W = [np.linspace(1.0, 0.5, 64 - 7), np.ones(10)]
     base = dict(n_in=[64, 10, 5], n=[64, 16, 8], T=[2, 1, 1], x=np.zeros(2 * (2 * 64 + 10 + 5)), form=[1, 2, 0], g=[5.0, 67.9, 0.0],
@@ -66,48 +144,48 @@ def test_argument_validation_needs_no_gpu():
         return fc.raw_call(L, a["n_in"], a["n"], a["T"], a["x"], a["form"], a["g"], a["window_of"], a["windows"],
                            device=a.get("device", 0))[0]
 
-    def refused(code, word, **kw):
-        assert call(**kw) == code, kw
-        msg = L.nmrfit_last_error()
-        assert word in msg, (kw, msg)
+    def refused(key, **kw):
+        _refusal_is_the_recorded_one(key, call(**kw), L.nmrfit_last_error())
     assert call() in (_cabi.OK, _cabi.E_NO_DEVICE)
     assert call(form=[0, 0, 0], window_of=[-1, -1, -1], windows=[]) in (_cabi.OK, _cabi.E_NO_DEVICE)
     assert call(device=1 << 20) == _cabi.E_NO_DEVICE
     # those of nmrfit_fid_transform, with n >= n_in' in place of n >= n_in
-    refused(_cabi.E_INVALID, b"spectrum 1", T=[2, 0, 1])
-    refused(_cabi.E_INVALID, b"spectrum 2", n_in=[64, 10, -5])
-    refused(_cabi.E_INVALID, b"at least", n=[64, 8, 8])
-    assert call(n_in=[64, 10, 5], n=[64, 16, 4]) == _cabi.E_INVALID
-    refused(_cabi.E_UNSUPPORTED, b"power of two", n=[64, 16, 12])
-    refused(_cabi.E_UNSUPPORTED, b"power of two", n=[64, 16, 1 << 23])
+    refused("T = 0", T=[2, 0, 1])
+    refused("n_in = -5", n_in=[64, 10, -5])
+    refused("n < n_in', spectrum 1", n=[64, 8, 8])
+    refused("n < n_in', spectrum 2", n_in=[64, 10, 5], n=[64, 16, 4])
+    refused("n = 12", n=[64, 16, 12])
+    refused("n = 2^23", n=[64, 16, 1 << 23])
     # n >= n_in' is enough: 64 - 7 = 57 points fit a transform of 64, and would fit one of 64 with n_in = 64 only
     assert call(n=[64, 16, 8]) in (_cabi.OK, _cabi.E_NO_DEVICE)
-    refused(_cabi.E_INVALID, b"at least", n=[32, 16, 8])
+    refused("n < n_in', spectrum 0", n=[32, 16, 8])
     # the new ones
-    refused(_cabi.E_INVALID, b"form is 0", form=[1, 3, 0])
-    refused(_cabi.E_INVALID, b"form is 0", form=[-1, 2, 0])
+    refused("form = 3", form=[1, 3, 0])
+    refused("form = -1", form=[-1, 2, 0])
     for bad in (0.0, -1.0, np.nan, np.inf):
-        refused(_cabi.E_INVALID, b"spectrum 1", g=[5.0, bad, 0.0])
-        refused(_cabi.E_INVALID, b"group delay", g=[bad, 67.9, 0.0])
+        refused("g = %r, spectrum 1" % bad, g=[5.0, bad, 0.0])
+        refused("g = %r, spectrum 0" % bad, g=[bad, 67.9, 0.0])
     assert call(g=[5.0, 67.9, np.nan]) in (_cabi.OK, _cabi.E_NO_DEVICE)              # (not read where no form is set)
-    refused(_cabi.E_UNSUPPORTED, b"form 2", n_in=[48, 10, 5], windows=[np.ones(48 - 7), np.ones(10)])
-    assert b"spectrum 0" in L.nmrfit_last_error() and b"power of two" in L.nmrfit_last_error()
-    refused(_cabi.E_INVALID, b"2 floor(g + 2)", g=[31.0, 67.9, 0.0])                  # 64 < 2 * 33
+    refused("form 1 at 48 points", n_in=[48, 10, 5], windows=[np.ones(48 - 7), np.ones(10)])
+    refused("g = 31 at 64 points", g=[31.0, 67.9, 0.0])                                # 64 < 2 * 33
     assert call(g=[30.0, 67.9, 0.0], window_of=[-1, 1, -1]) in (_cabi.OK, _cabi.E_NO_DEVICE)      # 64 = 2 * 32
-    refused(_cabi.E_INVALID, b"2 floor(g + 2)", g=[1e300, 67.9, 0.0])
-    refused(_cabi.E_INVALID, b"window_of", window_of=[0, 2, -1])
-    refused(_cabi.E_INVALID, b"window_of", window_of=[-2, 1, -1])
-    refused(_cabi.E_INVALID, b"spectrum 0", window_of=[1, 1, -1])                     # 10 values for 57 points
-    refused(_cabi.E_INVALID, b"as many values", windows=[np.ones(64), np.ones(10)])   # n_in, not n_in'
+    refused("g = 1e300", g=[1e300, 67.9, 0.0])
+    refused("window_of = 2", window_of=[0, 2, -1])
+    refused("window_of = -2", window_of=[-2, 1, -1])
+    refused("10 values for 57 points", window_of=[1, 1, -1])
+    refused("64 values for 57 points", windows=[np.ones(64), np.ones(10)])             # n_in, not n_in'
     for bad in (np.nan, np.inf, -np.inf):
         w = np.ones(10)
         w[7] = bad
-        refused(_cabi.E_INVALID, b"not finite (window 1)", windows=[W[0], w])
+        refused("a window value is %r" % bad, windows=[W[0], w])
     # the limits: T n summed, with T n_in of a form-1 job on top
     one = dict(n_in=[1 << 22], x=np.zeros(2), form=[0], g=[1.0], window_of=[-1], windows=[])
-    refused(_cabi.E_UNSUPPORTED, b"at most", n=[1 << 22], T=[17], **one)
+    refused("17 x 2^22 values", n=[1 << 22], T=[17], **one)
     one["form"] = [1]
-    refused(_cabi.E_UNSUPPORTED, b"form 1", n=[1 << 22], T=[9], **one)                 # 9 (n + n_in) > 2^26
+    refused("9 x 2^22 values in form 1", n=[1 << 22], T=[9], **one)                    # 9 (n + n_in) > 2^26
+    # a call that is wrong in two ways: the first refusal of the header's order wins
+    refused("form = 3 and n = 12", form=[1, 3, 0], n=[64, 16, 12])
+    refused("a window value is nan and n = 12", windows=[W[0], np.full(10, np.nan)], n=[64, 16, 12])
     # null pointers
     p = _cabi.ptr
     i64, i32 = (lambda a: np.array(a, dtype=np.int64)), (lambda a: np.array(a, dtype=np.int32))
@@ -117,13 +195,13 @@ def test_argument_validation_needs_no_gpu():
     for at in (0, 1, 2, 3, 4, 5, 6, 10, 11, 12):
         args = list(ok)
         args[at] = None
-        assert L.nmrfit_fid_condition_transform(0, 1, *args) == _cabi.E_INVALID, at
-    assert L.nmrfit_fid_condition_transform(0, 0, *ok) == _cabi.E_INVALID
+        _refusal_is_the_recorded_one("argument %d null" % at, L.nmrfit_fid_condition_transform(0, 1, *args), L.nmrfit_last_error())
+    _refusal_is_the_recorded_one("K = 0", L.nmrfit_fid_condition_transform(0, 0, *ok), L.nmrfit_last_error())
     args = list(ok)
     args[7] = 1                                                                         # a window, but no arrays
-    assert L.nmrfit_fid_condition_transform(0, 1, *args) == _cabi.E_INVALID
+    _refusal_is_the_recorded_one("M = 1 without arrays", L.nmrfit_fid_condition_transform(0, 1, *args), L.nmrfit_last_error())
     args[7] = -1
-    assert L.nmrfit_fid_condition_transform(0, 1, *args) == _cabi.E_INVALID
+    _refusal_is_the_recorded_one("M = -1", L.nmrfit_fid_condition_transform(0, 1, *args), L.nmrfit_last_error())
 
 
 def test_python_argument_errors_come_before_the_library(monkeypatch):

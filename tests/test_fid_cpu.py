@@ -158,9 +158,42 @@ def test_table_and_header():
     assert nmrfit_amd.fid is fid and nmrfit_amd.spectra_from_fids is fid.spectra_from_fids
 
 
+# recorded from the library before the three entry points shared one body (tests/fid_support.refusal_table)
+REFUSALS = fs.refusal_table([
+    (_cabi.E_INVALID,
+     'nmrfit_fid_transform: the number of spectra must be > 0 and n_in, n, T, fid, u_out, v_out, rows_out '
+     'non-null',
+     ('n_in null', 'n null', 'T null', 'x null', 'u null', 'v null', 'rows null', 'K = 0', 'K = -3')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_transform: every spectrum needs T > 0 and n_in > 0 (spectrum 1)',
+     ('T = 0', 'n_in = -8', 'T = 0 and n = 6')),
+    (_cabi.E_INVALID,
+     'nmrfit_fid_transform: every spectrum needs T > 0 and n_in > 0 (spectrum 0)',
+     ('T = -1', 'n_in = 0')),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_transform: a transform length is at least the trace's length (spectrum 0)",
+     ('n < n_in, spectrum 0',)),
+    (_cabi.E_INVALID,
+     "nmrfit_fid_transform: a transform length is at least the trace's length (spectrum 1)",
+     ('n < n_in, spectrum 1',)),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_transform: a transform length is a power of two, 2 .. 2^22 (spectrum 1): zero fill to the'
+     ' next power of two',
+     ('n = 6', 'n = 12', 'n = 1', 'n = 4194306', 'n = 8388608')),
+    (_cabi.E_UNSUPPORTED,
+     'nmrfit_fid_transform: a call takes at most 65535 spectra and 67108864 transformed values (T n summed'
+     ' over the spectra)',
+     ('65536 spectra', '17 x 2^22 values', '2^26 + 2 values', '2^54 values')),
+])
+
+
+def _refusal_is_the_recorded_one(key, rc, message):
+    assert (rc, message.decode()) == REFUSALS[key], key
+
+
 def test_argument_validation_needs_no_gpu():
-    """Every refusal of the header comes back before anything touches a device; an impossible device index is answered
-    by the shared check with the message nmrfit_weights_build gives."""
+    """Every refusal of the header comes back before anything touches a device, with the code and the complete message of
+    REFUSALS; an impossible device index is answered by the shared check with the message nmrfit_weights_build gives."""
     L = _cabi.lib()
     p = _cabi.ptr
     i32, i64 = (lambda a: np.array(a, dtype=np.int32)), (lambda a: np.array(a, dtype=np.int64))
@@ -170,22 +203,29 @@ def test_argument_validation_needs_no_gpu():
 
     def call(device=0, K=2, n_in=n_in, n=n, T=T, x=x, u=u, v=v, rows=rows, Z=Z):
         return L.nmrfit_fid_transform(device, K, p(n_in), p(n), p(T), p(x), p(u), p(v), p(rows), p(Z))
+
+    def refused(key, rc):
+        _refusal_is_the_recorded_one(key, rc, L.nmrfit_last_error())
     for name in ("n_in", "n", "T", "x", "u", "v", "rows"):
-        assert call(**{name: None}) == _cabi.E_INVALID, name
-    assert call(K=0) == _cabi.E_INVALID and call(K=-3) == _cabi.E_INVALID
-    assert call(T=i32([2, 0])) == _cabi.E_INVALID and call(T=i32([-1, 1])) == _cabi.E_INVALID
-    assert call(n_in=i64([0, 8])) == _cabi.E_INVALID and call(n_in=i64([3, -8])) == _cabi.E_INVALID
-    assert call(n_in=i64([5, 8])) == _cabi.E_INVALID and b"at least" in L.nmrfit_last_error()
-    assert call(n_in=i64([3, 9]), n=i64([4, 8])) == _cabi.E_INVALID
+        refused(name + " null", call(**{name: None}))
+    refused("K = 0", call(K=0))
+    refused("K = -3", call(K=-3))
+    refused("T = 0", call(T=i32([2, 0])))
+    refused("T = -1", call(T=i32([-1, 1])))
+    refused("n_in = 0", call(n_in=i64([0, 8])))
+    refused("n_in = -8", call(n_in=i64([3, -8])))
+    refused("n < n_in, spectrum 0", call(n_in=i64([5, 8])))
+    refused("n < n_in, spectrum 1", call(n_in=i64([3, 9]), n=i64([4, 8])))
     for bad in (6, 12, 1, (1 << 22) + 2, 1 << 23):
-        assert call(n_in=i64([1, 1]), n=i64([4, bad])) == _cabi.E_UNSUPPORTED, bad
-        assert b"power of two" in L.nmrfit_last_error()
+        refused("n = %d" % bad, call(n_in=i64([1, 1]), n=i64([4, bad])))
     many = 65536
-    assert L.nmrfit_fid_transform(0, many, p(np.ones(many, dtype=np.int64)), p(np.full(many, 2, dtype=np.int64)),
-                                  p(np.ones(many, dtype=np.int32)), p(x), p(u), p(v), p(rows), None) == _cabi.E_UNSUPPORTED
-    assert call(n_in=i64([1, 1]), n=i64([1 << 22, 1 << 22]), T=i32([8, 9])) == _cabi.E_UNSUPPORTED
-    assert call(n_in=i64([1, 1]), n=i64([2, 2]), T=i32([1 << 25, 1])) == _cabi.E_UNSUPPORTED
-    assert call(n_in=i64([1, 1]), n=i64([1 << 22, 1 << 22]), T=i32([2 ** 31 - 1, 2 ** 31 - 1])) == _cabi.E_UNSUPPORTED
+    refused("65536 spectra", L.nmrfit_fid_transform(0, many, p(np.ones(many, dtype=np.int64)), p(np.full(many, 2, dtype=np.int64)),
+                                                    p(np.ones(many, dtype=np.int32)), p(x), p(u), p(v), p(rows), None))
+    refused("17 x 2^22 values", call(n_in=i64([1, 1]), n=i64([1 << 22, 1 << 22]), T=i32([8, 9])))
+    refused("2^26 + 2 values", call(n_in=i64([1, 1]), n=i64([2, 2]), T=i32([1 << 25, 1])))
+    refused("2^54 values", call(n_in=i64([1, 1]), n=i64([1 << 22, 1 << 22]), T=i32([2 ** 31 - 1, 2 ** 31 - 1])))
+    # a call that is wrong in two ways: the first refusal of the header's order wins
+    refused("T = 0 and n = 6", call(T=i32([2, 0]), n_in=i64([1, 1]), n=i64([4, 6])))
     # valid calls: what is reported then is the missing device (or, with a GPU, nothing)
     assert call() in (_cabi.OK, _cabi.E_NO_DEVICE)
     assert call(Z=None) in (_cabi.OK, _cabi.E_NO_DEVICE)

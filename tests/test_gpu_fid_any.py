@@ -13,6 +13,8 @@ the lengths that are not powers of two, in the library call that conditions and 
     power-of-two jobs of the batch are nmrfit_fid_condition_transform's bit for bit;
   * three child processes -- NMRFIT_POISON_ALLOC unset, 255, 63 -- give byte-identical outputs over the mixed batch;
   * an all-zero FID gives row status 1, a NaN input status 2 with u, v NaN, at N = 12.
+  * ties across the chunks of the partial maxima (fid_max_part_kernel serves the finish-only jobs by a remainder and the
+    others by a mask, in one launch): equal traces on both sides of a chunk boundary and across it, the first one wins.
 
 Measured on the MI355X (the worst ratio error / bar): see DESIGN.md 4.15.2.
 """
@@ -164,3 +166,24 @@ def test_statuses_at_twelve_points():
     assert fs.same_result(got[2], fid.transform_many([good], any_length=True, return_transform=True)[0])
     with pytest.raises(ValueError, match="FID 0 is all zero"):
         nmrfit_amd.spectra_from_fids([zero], 1.0, 1.0, 0.0, zero_fill=12, any_length=True)
+
+
+def test_ties_across_the_chunks_of_the_partial_maxima():
+    """fa.TIES: N = 12 (a finish-only job) and n = 8 in one call, each a stack of two sample traces lo and hi = 3 lo.  The
+    copies of hi transform to the same bits (asserted on the returned Y), so the maximum ties between them: the row is
+    the mirror's on that Y bit for bit, its index lies in the first copy -- before the chunk boundary, in the trace that
+    straddles it, behind it -- and a FID alone gives what it gives in the pair."""
+    los = [fs.sample_fid(n, 1, seed=97) for _, n, _, _ in fa.TIES]
+    for case in range(3):
+        xs = [fa.tie_stack(lo, T, placements[case]) for lo, (_, _, T, placements) in zip(los, fa.TIES)]
+        pair = fid.transform_many(xs, any_length=True, return_transform=True)
+        for x, (name, n, T, placements), (u, v, row, Y) in zip(xs, fa.TIES, pair):
+            hi_at = placements[case]
+            assert Y.shape == (T, n) and row[0] == 0 and row[4] == n and row[5] == T
+            assert all(fs.same_bits(Y[t], Y[hi_at[0]]) for t in hi_at), (name, hi_at)
+            lo_at = [t for t in range(T) if t not in hi_at]
+            assert all(fs.same_bits(Y[t], Y[lo_at[0]]) for t in (lo_at[1], 8192 // n - 1, lo_at[-1])) and not fs.same_bits(Y[0], Y[hi_at[0]])
+            _finish_is_the_hosts(u, v, row, Y)
+            assert int(row[3]) // n == hi_at[0], (name, hi_at, row)
+            alone = fid.transform_many([x], any_length=True, return_transform=True)[0]
+            assert fs.same_result(alone, (u, v, row, Y)), (name, hi_at)

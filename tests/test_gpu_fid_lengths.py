@@ -113,7 +113,7 @@ def test_an_impulse_at_zero_is_a_constant_exactly_and_the_tie_goes_to_index_zero
 # ---- C3: chirp-z at every M it can reach -------------------------------------------------------------------------------
 
 def _chirp_traces(N):
-    """T of the dense job: 1 from M = 2^20 up, 3 at 65467 (a chunk of fida_max_part_kernel's 8192 values straddles two
+    """T of the dense job: 1 from M = 2^20 up, 3 at 65467 (a chunk of fid_max_part_kernel's 8192 values straddles two
     traces at every boundary: 65467 is odd), else 2."""
     return 1 if fid.conv_length(N) >= 1 << 20 else (3 if N == 65467 else 2)
 
