@@ -162,6 +162,12 @@ LSQ_SIGNATURES = {
     "nmrfit_jacobian": [_VP, _I32, _VP, _VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP],
     "nmrfit_batch_normal_equations": [_VP, _VP, _VP, _VP, _VP, _VP, _VP],
 }
+# LSQ_ANALYTIC_SIGNATURES: include/nmrfit_amd_lsq_analytic.h (J, r and the normal equations from the closed-form
+# derivatives of the real-channel residual: one pass over the resident spectrum, no residual rows)
+LSQ_ANALYTIC_SIGNATURES = {
+    "nmrfit_jacobian_analytic": [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    "nmrfit_batch_normal_equations_analytic": [_VP, _VP, _VP, _VP, _VP],
+}
 # LSQ_IM_SIGNATURES: include/nmrfit_amd_lsq_im.h (the same on both channels of a fit_im fit: imaginary residual rows, the
 # Jacobian and the normal equations per channel)
 LSQ_IM_SIGNATURES = {
@@ -319,7 +325,7 @@ def lib():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         L = ctypes.CDLL(path)
         for name, argtypes in list(ALL_SIGNATURES.items()) + list(PREP_SIGNATURES.items()) + list(LSQ_SIGNATURES.items()) \
-                + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
+                + list(LSQ_ANALYTIC_SIGNATURES.items()) + list(LSQ_IM_SIGNATURES.items()) + list(NOISE_SIGNATURES.items()) + list(QUALITY_SIGNATURES.items()) \
                 + list(BASELINE_SIGNATURES.items()) + list(COV_SIGNATURES.items()) + list(COV_IM_SIGNATURES.items()) \
                 + list(FID_SIGNATURES.items()) + list(FID_COND_SIGNATURES.items()) + list(FID_ANY_SIGNATURES.items()):
             fn = getattr(L, name)

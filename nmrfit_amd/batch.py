@@ -266,7 +266,7 @@ class FitBatch:
                 for k in range(self.K)]
 
     # -- least squares (include/nmrfit_amd_lsq.h) --------------------------------------------------
-    def normal_equations(self, X, channels="real"):
+    def normal_equations(self, X, channels="real", jac="2-point"):
         """Per fit ``(A, g, f)`` at the K parameter vectors ``X``: the forward-difference rows ``lsq.ResidualModel``
         would make for each fit's box, their residual rows for ALL fits in one launch over the batch's resident spectra,
         A = J^T J and g = J^T r reduced on the device (csrc/lsq.hip), f the launch's own objective value at X[k].
@@ -276,12 +276,34 @@ class FitBatch:
         ``channels="both"`` (a batch created with a ``fit_im`` mode; nmrfit_batch_normal_equations_im): the rows of both
         channels in the same launch, A and g per channel, and per fit the combined ``(H, grad f, f)`` of the objective
         f = (rho_re + rho_im)/2 the batch's swarms minimise (``lsq.combine_channels``) -- bit-identical to
-        ``lsq.ResidualModel(Evaluator(spectrum), lower, upper, fit_im=mode).normal_equations(X[k])``."""
+        ``lsq.ResidualModel(Evaluator(spectrum), lower, upper, fit_im=mode).normal_equations(X[k])``.
+
+        ``jac="analytic"`` (``channels="real"``; nmrfit_batch_normal_equations_analytic, csrc/lsq_analytic.hip): A, g and
+        f = ||r|| from the closed-form derivatives of the residual in one pass over the resident spectra -- no residual
+        rows, no steps; bit-identical to ``Evaluator(spectrum).jacobian_analytic(X[k], normal=True)`` fit by fit, in any
+        batch.  A point with a width of zero or below the kernels' floor is refused."""
         from . import lsq
         if channels not in ("real", "both"):
             raise ValueError('FitBatch.normal_equations: channels is "real" or "both"')
+        if lsq._jac_form("FitBatch.normal_equations", jac) == "analytic" and channels == "both":
+            raise ValueError('FitBatch.normal_equations: jac="analytic" covers the real channel only (channels="real")')
         if len(X) != self.K:
             raise ValueError("FitBatch.normal_equations: one parameter vector per fit")
+        if jac == "analytic":
+            xs = []
+            for k, x in enumerate(X):
+                x = _cabi.f64(x)
+                if x.shape != (self.D[k],):
+                    raise ValueError("FitBatch.normal_equations: fit %d takes %d parameters" % (k, self.D[k]))
+                xs.append(x)
+            xs = np.concatenate(xs)
+            D = np.asarray(self.D, dtype=np.int64)
+            aoff = np.concatenate(([0], np.cumsum(D * D)))
+            A, g, f = np.empty(int(aoff[-1])), np.empty(int(self.offsets[-1])), np.empty(self.K)
+            _cabi.check(self._lib.nmrfit_batch_normal_equations_analytic(self._h, _cabi.ptr(xs), _cabi.ptr(A), _cabi.ptr(g),
+                                                                         _cabi.ptr(f)))
+            return [(A[aoff[k]:aoff[k + 1]].reshape(self.D[k], self.D[k]), g[self.offsets[k]:self.offsets[k + 1]], float(f[k]))
+                    for k in range(self.K)]
         rows, cs = [], []
         s = 1.0 / np.sqrt(self.Ns.astype(np.float64))
         for k, x in enumerate(X):
@@ -412,15 +434,23 @@ class FitBatch:
         return [uncertainty.covariance(A, M, g, X[k], self.lowers[k], self.uppers[k], sigma=(float(su[k]), float(sv[k])))
                 for k, (A, M, g, _) in enumerate(got)]
 
-    def polish(self, X=None, which=None, channels="real", **kwargs):
+    def polish(self, X=None, which=None, channels="real", jac="2-point", **kwargs):
         """Least-squares refinement of the K fits in lock step (``lsq.lm_polish`` over ``normal_equations``): every
         launch evaluates the trial points of all fits still moving.  ``X`` None: from ``best()``.  ``which``: the fits
         to refine (default all); the others come back as they are.  Real-part objective only (fit_im=False batches).
         Returns per fit ``(x, f)``, f the rows launch's objective value at x -- never above the start's.
 
         ``channels="both"`` (a batch created with a ``fit_im`` mode): the same loop over the combined normal equations
-        of both channels -- it minimises the objective the batch's swarms minimised, f = (rho_re + rho_im)/2."""
+        of both channels -- it minimises the objective the batch's swarms minimised, f = (rho_re + rho_im)/2.
+
+        ``jac="analytic"`` (``channels="real"``): the loop runs over the analytic normal equations (one pass per step
+        instead of D + 1 residual rows) and compares their own f = ||r||, the start's included.  After it ONE forward
+        call at the final points gives the rows launch's f, which is what comes back; a fit whose closing f is not below
+        its start's keeps its start.  (The two f of one point agree to rounding.  Only where a fit's whole gain is within
+        1e-9 of its f -- far above what separates the two sums -- a second forward call, at the start points, decides.)"""
         from . import lsq
+        if lsq._jac_form("FitBatch.polish", jac) == "analytic" and channels == "both":
+            raise ValueError('FitBatch.polish: jac="analytic" covers the real channel only (channels="real")')
         start = self.best()
         if X is None:
             X = [x for x, _ in start]
@@ -436,13 +466,35 @@ class FitBatch:
             for k, x in zip(which, trial):
                 if x is not None:
                     full[k] = x
-            got = self.normal_equations(full, channels=channels)
+            got = self.normal_equations(full, channels=channels, jac=jac)
             return [None if x is None else got[k] for k, x in zip(which, trial)]
         Xw, fw, info = lsq.lm_polish(provider, [X[k] for k in which], [self.lowers[k] for k in which],
                                      [self.uppers[k] for k in which], **kwargs)
         out = [(x, fk) for x, (_, fk) in zip(X, start)]
-        for k, x, fk in zip(which, Xw, fw):
-            out[k] = (x, float(fk))
+        if jac == "analytic":
+            # the rows launch's f at the final points; where a fit has moved, it must lie below the start's
+            X0 = [np.clip(X[k], self.lowers[k], self.uppers[k]) for k in which]
+            full = [x.copy() for x in X]
+            for k, x in zip(which, Xw):
+                full[k] = x
+            closing = self.normal_equations(full, channels=channels)
+            f_an0 = [h[0] for h in info["history"]]
+            moved = [i for i, n in enumerate(info["accepted"]) if n > 0]
+            opening = None
+            if any(not closing[which[i]][2] < f_an0[i] * (1.0 - 1e-9) for i in moved):
+                for k, x in zip(which, X0):
+                    full[k] = x
+                opening = self.normal_equations(full, channels=channels)
+            for i, k in enumerate(which):
+                if i in moved and opening is not None and not closing[k][2] < opening[k][2]:
+                    out[k] = (X0[i], float(opening[k][2]))
+                else:
+                    out[k] = (Xw[i], float(closing[k][2]))
+            info["kept_start"] = [i in moved and opening is not None and not closing[which[i]][2] < opening[which[i]][2]
+                                  for i in range(len(which))]
+        else:
+            for k, x, fk in zip(which, Xw, fw):
+                out[k] = (x, float(fk))
         self.last_polish = info
         return out
 

@@ -36,7 +36,7 @@ def fit(data, lower, upper, expon=0.5, dynamic_weighting=True, fit_im=False, pro
 
 
 def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=False, channel=None, device_weights=False,
-             batch_polish=False, quality=False, residual_baseline=None, uncertainty=None, **kwargs):
+             batch_polish=False, quality=False, residual_baseline=None, uncertainty=None, polish_jac="2-point", **kwargs):
     """Fit several spectra: ``jobs`` is a sequence of ``(data, lower, upper)`` triples (or dicts of ``fit``'s
     arguments); every job is fitted as ``fit`` would fit it with the same keyword arguments, and the list of
     FitUtility objects comes back in the order of ``jobs``.  Not in the reference (its users loop over
@@ -98,6 +98,11 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
       the per-fit path refines the real channel and can only accept or reject against it.  ``error`` is that objective
       at the accepted point, never above the swarm's.  ``fit_im=False`` jobs behave as under ``True``; fits that end
       up alone and batches with any D > 76 keep the per-fit path.
+    * ``polish_jac="analytic"``: every polish of the call takes the closed-form Jacobian of the real-channel residual
+      (include/nmrfit_amd_lsq_analytic.h, csrc/lsq_analytic.hip) instead of the forward differences of D + 1 residual
+      rows -- ``FitBatch.polish(jac="analytic")`` under ``batch_polish=True``, ``lsq.polish(jac="analytic")`` on the
+      per-fit path.  ``error`` is still the rows launch's value at the accepted point, never above the swarm's.  Real
+      channel only: with ``batch_polish="both"`` it raises ValueError up front.  Default "2-point": as ever.
     * ``quality=True``: every returned fit carries ``fit.quality`` (``nmrfit_amd.quality.FitQuality``): the residual
       V_fit - V_data at its FINAL ``params`` reduced on the device per peak region (the peaks' bounds), over the whole
       grid and over what no region holds -- (P + 2) rows of 64 bytes per fit instead of the arrays of ``generate`` --
@@ -136,9 +141,15 @@ def fit_many(jobs, threads=4, batch=True, shard=False, devices=None, generate=Fa
     from . import baseline as _baseline, uncertainty as _uncertainty
     kwargs.setdefault("summary", False)
     jobs = [dict(job) if isinstance(job, dict) else dict(zip(("data", "lower", "upper"), job)) for job in jobs]
+    if polish_jac not in ("2-point", "analytic"):
+        raise ValueError('fit_many: polish_jac is "2-point" or "analytic"')
+    if polish_jac == "analytic" and isinstance(batch_polish, str) and batch_polish == "both":
+        raise ValueError('fit_many: polish_jac="analytic" covers the real channel only: not with batch_polish="both"')
     call = _Call(threads, batch, kwargs, 1 if generate is True else generate, bool(device_weights),
                  "both" if isinstance(batch_polish, str) and batch_polish == "both" else bool(batch_polish), bool(quality),
-                 _baseline.option(residual_baseline), _uncertainty.option(uncertainty))
+                 _baseline.option(residual_baseline), polish_jac, _uncertainty.option(uncertainty))
+    if polish_jac == "analytic" and call.uncertainty is not None and call.uncertainty.get("channels", "real") == "both":
+        raise ValueError('fit_many: polish_jac="analytic" covers the real channel only: not with uncertainty channels="both"')
     if call.uncertainty is not None:
         from .equations import fit_im_mode
         for m, job in enumerate(jobs):
@@ -178,6 +189,7 @@ class _Call(typing.NamedTuple):
     batch_polish: object         # False, True (fit_im=False jobs), or "both" (the jobs of fit_im batches too, on both channels)
     quality: bool = False        # every fit gets ``quality``: its residual statistics per peak region (quality.py)
     residual_baseline: object = None   # None, or baseline.option()'s dict: every fit gets ``residual_baseline`` (baseline.py)
+    polish_jac: str = "2-point"  # the Jacobian of every polish: "2-point" (D + 1 residual rows) or "analytic" (lsq_analytic.hip)
     uncertainty: object = None   # None, or uncertainty.option()'s dict: every fit gets ``uncertainty`` (uncertainty.py)
 
 
@@ -356,6 +368,8 @@ class _Batch:
                 both = call.batch_polish == "both"
                 which = [k for k, f in enumerate(fits) if f.options.get('polish', False) and (both or not f.fit_im)]
                 kw = dict(channels="both") if any(fits[k].fit_im for k in which) else {}
+                if call.polish_jac != "2-point":
+                    kw["jac"] = call.polish_jac
                 # (the launch covers the whole batch: one fit beyond the kernel's D leaves all of them to the per-fit path)
                 if which and max(len(f.lower) for f in fits) <= _cabi.LSQ_MAX_D:
                     new = fb.polish([x for x, _ in best], which=which, **kw)
@@ -384,8 +398,10 @@ class _Batch:
         fits, plans = self.fits, self.plans
         per_fit = [k for k, f in enumerate(fits) if f.options.get('polish', False) and k not in refined]
         if per_fit:
+            kw = {} if call.polish_jac == "2-point" else dict(jac=call.polish_jac)
+
             def refine(k):
-                return fits[k]._polish(best[k][0], best[k][1], plans[k])
+                return fits[k]._polish(best[k][0], best[k][1], plans[k], **kw)
             if call.threads > 1 and len(per_fit) > 1:
                 with ThreadPoolExecutor(max_workers=int(call.threads)) as pool:
                     new = list(pool.map(refine, per_fit))

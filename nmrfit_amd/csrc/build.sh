@@ -15,7 +15,7 @@ mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 EXTRA=()
 LIBNAME="${NMRFIT_LIBNAME:-libnmrfit_amd.so}"
-UNITS=(objective objective_default objective_farfield objective_farfield32 objective_norec objective_pair objective_rows_im objective_batch objective_batch_im objective_batch_im2 objective_batch_im2f pso batch batch_create batch_lsq batch_data result phase peaks weights noise quality baseline fid fid_cond fid_any fid_call lsq lsq_cov lsq_cov_im host_call ctx ctx_eval comm)
+UNITS=(objective objective_default objective_farfield objective_farfield32 objective_norec objective_pair objective_rows_im objective_batch objective_batch_im objective_batch_im2 objective_batch_im2f pso batch batch_create batch_lsq batch_data result phase peaks weights noise quality baseline fid fid_cond fid_any fid_call lsq lsq_cov lsq_cov_im lsq_analytic host_call ctx ctx_eval comm)
 for arg in "$@"; do
     if [ "$arg" = "--ab" ]; then
         EXTRA+=(-DNMRFIT_AB_BUILD)

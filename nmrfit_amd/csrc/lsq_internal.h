@@ -107,6 +107,28 @@ int check_sigma(const char *who, double sigma_u, double sigma_v);
 // J and r alone for one fit of any D (no LDS tile): what nmrfit_jacobian runs beyond kLsqMaxD
 int launch_lsq_plain(hipStream_t st, const LsqJob &job);
 
+// One fit of an analytic launch (lsq_analytic.hip; include/nmrfit_amd_lsq_analytic.h): no residual rows -- the kernel forms
+// [J | r] from the fit's resident arrays (grid_slot order, as the objective kernels read them) and x.
+struct LsqAnalyticJob {
+    const double *wc, *u, *v, *wt;
+    const double *x;       // D = 4 + 3 P parameters, device memory
+    double w0, s;
+    int64_t N;
+    int32_t P, D;
+    int32_t nseg, seg_tiles;   // lsq_segments(N)
+    double *J;             // N x D row-major, or null
+    double *r;             // N, or null
+    double *partial;       // nseg x lsq_sums_analytic(D), or null: no sums
+    double *A;             // D x D, or null
+    double *g;             // D, or null
+    double *f;             // 1, or null
+};
+// the sums of an analytic job: lsq_sums(D) and one more entry, the pair (D, D) = sum_j r_j^2
+inline int64_t lsq_sums_analytic(int64_t D) { return lsq_sums(D) + 1; }
+static_assert(kLsqThreads * kLsqAcc >= kLsqMaxD * (kLsqMaxD + 1) / 2 + kLsqMaxD + 1, "accumulators for the largest D and f");
+// J, r and -- where a job has `partial` -- A, g and f of K fits (jobs: device memory), on `st`.  Dmax <= kLsqMaxD.
+int launch_lsq_analytic(hipStream_t st, const LsqAnalyticJob *d_jobs, int32_t K, int32_t Dmax, bool sums);
+
 // One fit of a residual-rows launch over a batch's resident spectra: the grid as BatchFit holds it, S parameter rows
 // X [S x D], their objective values f [S] and residual rows R [S x N].  A batch with an imaginary-channel mode may ask for
 // the rows of both channels instead (launch_rows_batch, fit_im 1 or 2): R is then [2][S][N], the imaginary rows second,

@@ -198,6 +198,31 @@ class Evaluator:
         the objective value of row 0."""
         return self._jacobian("jacobian", False, None, rows, c, s, J, r, normal)
 
+    def jacobian_analytic(self, x, J=False, r=False, normal=False):
+        """``nmrfit_jacobian_analytic`` (include/nmrfit_amd_lsq_analytic.h): the closed-form derivatives of the
+        real-channel residual at the ONE parameter vector ``x`` -- no residual rows, no steps.  Returns a dict with what
+        was asked for -- ``J`` [N, D] (row-major), ``r`` [N] (||r|| is the objective), ``A`` [D, D] = J^T J and ``g`` [D]
+        = J^T r (``normal``) -- and with ``normal`` also ``f`` = sqrt(sum r^2), the call's own sum.  Whatever kernel
+        variant the context is set to.  D <= 76; a width of zero or below the kernels' floor, or a parameter that is not
+        finite, is refused."""
+        x = _cabi.f64(x)
+        if x.ndim != 1 or x.size < 4 or (x.size - 4) % 3:
+            raise ValueError("jacobian_analytic: x is one parameter vector of 4 + 3 P entries")
+        D, P = x.size, (x.size - 4) // 3
+        out = {}
+        f = np.empty(1) if normal else None
+        if J:
+            out["J"] = np.empty((self.N, D))
+        if r:
+            out["r"] = np.empty(self.N)
+        if normal:
+            out["A"], out["g"] = np.empty((D, D)), np.empty(D)
+        _cabi.check(self._lib.nmrfit_jacobian_analytic(self._ctx, P, _cabi.ptr(x), *(_cabi.ptr(out.get(k)) for k in ("J", "r", "A", "g")),
+                                                       _cabi.ptr(f)))
+        if normal:
+            out["f"] = float(f[0])
+        return out
+
     def sandwich(self, rows, c, s, sigma_u, sigma_v):
         """``nmrfit_sandwich`` (include/nmrfit_amd_cov.h): a dict with ``A`` = J^T J, ``M`` = J^T diag(q) J -- q_j the
         variance of the weighted residual at grid point j under noise (sigma_u, sigma_v) on the two channels, from the

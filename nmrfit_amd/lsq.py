@@ -27,6 +27,13 @@ makes of them the gradient of f in the forward-difference model and a positive s
 Gauss-Newton Hessian, the ``(H, grad f, f)`` that ``lm_polish`` takes as it is.  ``ResidualModel(..., fit_im=mode)``,
 ``polish(..., channels="both")``, ``FitBatch.polish(channels="both")`` and ``fit_many(batch_polish="both")`` are the ways in;
 every default is the real channel alone, as before.
+
+The analytic Jacobian (``nmrfit_jacobian_analytic``, csrc/lsq_analytic.hip; include/nmrfit_amd_lsq_analytic.h).  The
+derivative of the pseudo-Voigt residual is elementary: ``jac="analytic"`` (``ResidualModel``, ``least_squares``,
+``polish``, ``FitBatch.normal_equations`` / ``polish``, ``fit_many(polish_jac=...)``) forms J, r and the normal equations
+in ONE pass over the resident spectrum -- no D + 1 residual rows, no steps, no flipped steps at the upper bound -- with
+f = ||r|| the call's own sum; ``jacobian_host`` states the same quantities in numpy and ``analytic_provider`` feeds
+``lm_polish`` from them.  Real channel only; every default stays "2-point".
 """
 import numpy as np
 
@@ -60,6 +67,48 @@ def normal_equations_host(R, c, s):
     r = R[0] * s
     J = np.ascontiguousarray(((R[1:] - R[0]) * c[:, None]).T)
     return J.T @ J, J.T @ r, J, r
+
+
+def jacobian_host(x, w, u, v, weights):
+    """What csrc/lsq_analytic.hip computes, in numpy: ``(J, r)`` at the parameter vector ``x`` -- r = s weights (V -
+    model) [N], s = 1/sqrt(N), and J [N x D] its closed-form derivatives (include/nmrfit_amd_lsq_analytic.h states them),
+    t formed from the centred grid as the kernels form it.  A width of zero or below the kernels' floor is the caller's
+    to avoid (the device call refuses it)."""
+    x, w, u, v = (np.asarray(q, dtype=np.float64) for q in (x, w, u, v))
+    N, D = w.size, x.size
+    P = (D - 4) // 3
+    wt = np.ones(N) if weights is None else np.asarray(weights, dtype=np.float64)
+    w0 = w[N // 2]
+    wc = w - w0
+    frac = np.arange(N, dtype=np.float64) / float(N)
+    phi = x[0] + x[1] * frac
+    sn, cs = np.sin(phi), np.cos(phi)
+    V, I = cs * u - sn * v, sn * u + cs * v
+    q = wt * (1.0 / np.sqrt(N))
+    r, yoff = x[2], x[3]
+    ln2 = float(np.log(2.0))
+    J = np.empty((N, D))
+    model = np.zeros(N)
+    d_r = np.zeros(N)
+    for k in range(P):
+        width, loc, a = x[4 + 3 * k:7 + 3 * k]
+        ihw = 2.0 / width
+        t = (wc - (loc - w0)) * ihw
+        t2 = t * t
+        iS = 1.0 / (1.0 + t2)
+        e = np.exp2(-t2)
+        Lh, Gh = ihw / np.pi * iS, ihw * np.sqrt(ln2 / np.pi) * e
+        L, G = a * r * Lh, a * (1.0 - r) * Gh
+        model += L + G
+        d_r += a * (Lh - Gh)
+        J[:, 4 + 3 * k] = q * (0.5 * ihw) * (L * (1.0 - t2) * iS + G * (1.0 - 2.0 * ln2 * t2))
+        J[:, 5 + 3 * k] = -q * (2.0 * ihw * t) * (L * iS + ln2 * G)
+        J[:, 6 + 3 * k] = -q * (r * Lh + (1.0 - r) * Gh)
+    J[:, 0] = -q * I
+    J[:, 1] = -q * I * frac
+    J[:, 2] = -q * d_r
+    J[:, 3] = -q * float(P)
+    return J, q * (V - (model + P * yoff))     # (the reference adds yoff once per peak)
 
 
 def normal_equations_host_im(R_re, R_im, c, s):
@@ -98,15 +147,28 @@ def combine_channels(parts):
     return H, grad, f
 
 
+def _jac_form(who, jac):
+    if jac not in ("2-point", "analytic"):
+        raise ValueError('%s: jac is "2-point" or "analytic"' % who)
+    return jac
+
+
 class ResidualModel:
     """fun / jac callables over an ``equations.Evaluator``.  ``fit_im`` 0 (default): the real channel, as ever.  With a
     mode (True / "sum"): ``fun`` is the stacked 2N vector [r_re; r_im], ``jac`` the stacked 2N x D matrix (J_re above
     J_im, one ``nmrfit_jacobian_im`` call) -- scipy's TRF then minimises rho_re^2 + rho_im^2 -- and ``normal_equations``
-    the combined ``(H, grad f, f)`` of the objective itself (``combine_channels``)."""
+    the combined ``(H, grad f, f)`` of the objective itself (``combine_channels``).
 
-    def __init__(self, evaluator, lower=None, upper=None, rel_step=_SQRT_EPS, fit_im=0):
+    ``jac="analytic"`` (real channel only): ``jac`` and ``normal_equations`` are the closed-form derivatives of ONE
+    ``nmrfit_jacobian_analytic`` call at x -- f is then that call's own ||r|| -- while ``fun`` stays the rows launch;
+    ``sandwich`` / ``sandwich_im`` are the forward-difference model's alone."""
+
+    def __init__(self, evaluator, lower=None, upper=None, rel_step=_SQRT_EPS, fit_im=0, jac="2-point"):
         from .equations import fit_im_mode
         self.fit_im = fit_im_mode(fit_im)
+        self.jac_form = _jac_form("ResidualModel", jac)
+        if self.jac_form == "analytic" and self.fit_im:
+            raise ValueError('ResidualModel: jac="analytic" covers the real channel only (fit_im=False)')
         self.ev = evaluator
         self.N = evaluator.N
         self.lower = None if lower is None else _cabi.f64(lower)
@@ -142,6 +204,8 @@ class ResidualModel:
         """[fun(x + h_i e_i) - fun(x)] / h_i as N x D: one launch of the D + 1 residual rows, J formed on the
         device from them (csrc/lsq.hip) -- the bits of ``(R[1:] - R[0]) * (scale / h)`` transposed."""
         self.n_jac += 1
+        if self.jac_form == "analytic":
+            return self.ev.jacobian_analytic(x, J=True)["J"]
         rows, h = self.rows(x)
         if self.fit_im:   # [2, N, D] as it arrives is J_re above J_im
             return self.ev.jacobian_im(rows, self._scale / h, self._scale, self.fit_im, J=True)["J"].reshape(2 * self.N, -1)
@@ -151,6 +215,9 @@ class ResidualModel:
         """``(A, g, f)`` at x: A = J^T J [D x D], g = J^T fun(x) [D] reduced on the device in a fixed order, and f the
         objective value the same launch returns for x.  D <= 76."""
         self.n_jac += 1
+        if self.jac_form == "analytic":
+            out = self.ev.jacobian_analytic(x, normal=True)
+            return out["A"], out["g"], out["f"]
         rows, h = self.rows(x)
         if self.fit_im:
             out = self.ev.jacobian_im(rows, self._scale / h, self._scale, self.fit_im, normal=True)
@@ -165,6 +232,8 @@ class ResidualModel:
         ``fit_im`` mode has ``sandwich_im``."""
         if self.fit_im:
             raise ValueError("ResidualModel.sandwich: the covariance covers the real channel only (fit_im=False)")
+        if self.jac_form == "analytic":
+            raise ValueError('ResidualModel.sandwich: the meat is made of the forward-difference rows (jac="2-point")')
         self.n_jac += 1
         rows, h = self.rows(x)
         out = self.ev.sandwich(rows, self._scale / h, self._scale, sigma_u, sigma_v)
@@ -177,6 +246,8 @@ class ResidualModel:
         takes both.  D <= 76."""
         if not self.fit_im:
             raise ValueError("ResidualModel.sandwich_im: the model was made without a fit_im mode: sandwich is its call")
+        if self.jac_form == "analytic":
+            raise ValueError('ResidualModel.sandwich_im: the meat is made of the forward-difference rows (jac="2-point")')
         self.n_jac += 1
         rows, h = self.rows(x)
         out = self.ev.sandwich_im(rows, self._scale / h, self._scale, self.fit_im, sigma_u, sigma_v)
@@ -186,13 +257,14 @@ class ResidualModel:
         return float(np.linalg.norm(self.fun(x)))
 
 
-def least_squares(evaluator, x0, lower, upper, fit_im=0, **kwargs):
+def least_squares(evaluator, x0, lower, upper, fit_im=0, jac="2-point", **kwargs):
     """scipy.optimize.least_squares with GPU residuals / Jacobian.  Returns the scipy result;
     ``result.cost`` is 0.5*objective**2 and ``result.objective`` the RMSE the swarm minimises.  ``fit_im`` (a mode):
-    the stacked residual of both channels -- ``result.objective`` is then sqrt(rho_re^2 + rho_im^2)."""
+    the stacked residual of both channels -- ``result.objective`` is then sqrt(rho_re^2 + rho_im^2).  ``jac``: "2-point"
+    (the forward-difference Jacobian from D + 1 residual rows) or "analytic" (the closed forms, real channel only)."""
     from scipy.optimize import least_squares as _ls
     lower, upper = _cabi.f64(lower), _cabi.f64(upper)
-    model = ResidualModel(evaluator, lower, upper, fit_im=fit_im)
+    model = ResidualModel(evaluator, lower, upper, fit_im=fit_im, jac=jac)
     x0 = np.clip(np.asarray(x0, dtype=np.float64), lower, upper)
     kwargs.setdefault("method", "trf")
     kwargs.setdefault("x_scale", np.maximum(upper - lower, 1e-12))
@@ -202,7 +274,7 @@ def least_squares(evaluator, x0, lower, upper, fit_im=0, **kwargs):
     return res
 
 
-def polish(evaluator, x_swarm, lower, upper, fit_im=False, channels="real", **kwargs):
+def polish(evaluator, x_swarm, lower, upper, fit_im=False, channels="real", jac="2-point", **kwargs):
     """Refine a swarm result; keeps it if the least-squares step does not improve on it.
 
     The residual rows are the REAL-part residual only.  ``fit_im`` is the mode the swarm
@@ -212,10 +284,16 @@ def polish(evaluator, x_swarm, lower, upper, fit_im=False, channels="real", **kw
 
     ``channels="both"`` (with a ``fit_im`` mode): TRF on the stacked residual of both channels, [r_re; r_im] with
     J_re above J_im -- it minimises rho_re^2 + rho_im^2 where the swarm minimised (rho_re + rho_im)/2, close relatives
-    with the same zero; acceptance is on the swarm's objective as above."""
+    with the same zero; acceptance is on the swarm's objective as above.
+
+    ``jac="analytic"`` (``channels="real"``): TRF with the closed-form Jacobian; acceptance is unchanged."""
     x_swarm = np.asarray(x_swarm, dtype=np.float64)
     if channels not in ("real", "both"):
         raise ValueError('polish: channels is "real" or "both"')
+    if _jac_form("polish", jac) == "analytic":
+        if channels == "both":
+            raise ValueError('polish: jac="analytic" covers the real channel only (channels="real")')
+        kwargs["jac"] = jac
     if channels == "both":
         from .equations import fit_im_mode
         if not fit_im_mode(fit_im):
@@ -243,6 +321,21 @@ def rows_provider(residuals, lowers, uppers, rel_step=_SQRT_EPS):
             s = 1.0 / np.sqrt(R.shape[1])
             A, g, _, _ = normal_equations_host(R, s / h, s)
             out.append((A, g, float(f[0])))
+        return out
+    return provider
+
+
+def analytic_provider(jacobians):
+    """A ``provider`` for ``lm_polish`` from K callables ``jacobians[k](x) -> (J [N x D], r [N])`` (``jacobian_host`` on
+    a spectrum, or an ``Evaluator.jacobian_analytic(x, J=True, r=True)`` unpacked): A = J^T J, g = J^T r, f = ||r||."""
+    def provider(X):
+        out = []
+        for k, x in enumerate(X):
+            if x is None:
+                out.append(None)
+                continue
+            J, r = jacobians[k](x)
+            out.append((J.T @ J, J.T @ r, float(np.sqrt(r @ r))))
         return out
     return provider
 

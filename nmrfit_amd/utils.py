@@ -401,17 +401,18 @@ class FitUtility:
             ev.close()
         self._finish(xopt, fopt)
 
-    def _polish(self, xopt, fopt, plan):
+    def _polish(self, xopt, fopt, plan, jac="2-point"):
         """options['polish'] for a fit whose swarm ran in a device batch (core.fit_many): the same least-squares
         refinement fit() applies, on a context made like fit()'s (weights, kernel variant, imaginary-channel mode), so
         the polished answer is the lone call's bit for bit.  The trust-region iterations are scipy's, one fit at a time
-        on the host (each Jacobian is one launch of D + 1 residual rows): they do not run in lock step across fits."""
+        on the host (each Jacobian is one launch of D + 1 residual rows, or with ``jac="analytic"`` -- fit_many's
+        ``polish_jac`` -- one pass of csrc/lsq_analytic.hip): they do not run in lock step across fits."""
         from . import lsq
         ev = equations.Evaluator(self.data.w, self.data.u, self.data.v, self.weights, device=self._device())
         try:
             ev.set_fit_im(self.fit_im)
             ev.set_variant(plan['variant'])
-            xopt, fopt, _ = lsq.polish(ev, xopt, self.lower, self.upper, fit_im=self.fit_im)
+            xopt, fopt, _ = lsq.polish(ev, xopt, self.lower, self.upper, fit_im=self.fit_im, jac=jac)
         finally:
             ev.close()
         return xopt, fopt

@@ -29,7 +29,7 @@ def demangle(names):
 def resources(extra, units=()):
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for src in units or ("objective_default.hip", "objective_pair.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip", "lsq_cov.hip", "lsq_cov_im.hip", "baseline.hip"):
+        for src in units or ("objective_default.hip", "objective_pair.hip", "objective_farfield.hip", "objective_farfield32.hip", "objective_norec.hip", "objective_rows_im.hip", "objective_batch.hip", "objective_batch_im.hip", "objective_batch_im2.hip", "objective_batch_im2f.hip", "objective.hip", "pso.hip", "batch.hip", "phase.hip", "peaks.hip", "weights.hip", "lsq.hip", "lsq_cov.hip", "lsq_cov_im.hip", "lsq_analytic.hip", "baseline.hip"):
             if not os.path.exists(os.path.join(CSRC, src)):
                 continue
             cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
